@@ -10,12 +10,16 @@ and the solve, also after a rejected step, as the reference does.  F(x) and its 
 checkpoints depend on x alone and are kept from the evaluation that made them (the trial
 point's, or the trip before a rejection); the evaluation counter still counts F(x) per trip.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Per-kernel durations come from HIP events recorded on the
-solver's own stream during the timed steps (pnol_ctx_timer); `cpu_baseline` times the
-oracle (oracle/, the CPU restatement of the reference) on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W warmup trips, times K trips, writes
+the last timed solve's X, F0 and FOpt to DIR/<name>.npy when --dump-outputs is given, and
+prints the line; its per-kernel durations come from HIP events recorded on the solver's own
+stream during those timed steps (pnol_ctx_timer).  Everything that takes runs of its own --
+the BFGS H.g sweeps, the BFGS cfg-2 / BFGS_Bnd cfg-5 solves, rows mode beside the headline at
+N > 1, and `cpu_baseline` (the oracle, oracle/, the CPU restatement of the reference, on a
+bounded sample) -- runs only with --full; without it those keys of the line are null.
 """
 from __future__ import annotations
 
@@ -42,6 +46,11 @@ def _args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extras beside the headline: BFGS H.g sweeps, the BFGS cfg-2 / BFGS_Bnd cfg-5 "
+                         "solves, rows mode at N > 1, the CPU baseline (each can be switched off with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned (X, F0, FOpt) to DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-hg", action="store_true")
     ap.add_argument("--no-timers", action="store_true", help="no per-kernel HIP events in the timed region")
@@ -422,6 +431,26 @@ def cpu_baseline(m, n, budget_s=20.0):
     }
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000    # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """Write each named array as dirname/<name>.npy in float64.  Arrays are written whole while
+    they fit DUMP_BUDGET_BYTES together; otherwise every array longer than its equal share of the
+    budget is cut to a fixed sample of its flattened entries (sorted indices from
+    default_rng(0x5EED2018): the same entries in every run of the same arguments)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        share = DUMP_BUDGET_BYTES // (8 * len(arrays))
+        rng = np.random.default_rng(0x5EED2018)
+        for k, a in arrays.items():
+            if a.size > share:
+                arrays[k] = a.reshape(-1)[np.sort(rng.choice(a.size, size=share, replace=False))]
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def _free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -573,7 +602,7 @@ def main():
                                             F0.ctypes.data_as(dp), FO.ctypes.data_as(dp), m, C.byref(res), steps),
                 "pnol_run_levmarq")
         trips[:] = [steps[0], steps[1]]
-        return X
+        return X, F0, FO      # what a caller of the solve receives
 
     # warmup with every per-kernel timer on: the full breakdown (untimed); the timed region
     # keeps only the timers of the kernels priced below (each timer adds two event records
@@ -596,7 +625,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        Xr = run(args.steps)
+        out = run(args.steps)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -619,16 +648,19 @@ def main():
         else:
             pm = dict(pl)
         L.check(L.lib().pnol_ctx_enable_timers(dctx, 0), "timers")
-        return el, Xr, bd, pl, pm, list(trips)
+        return el, out, bd, pl, pm, list(trips)
 
-    elapsed, X, breakdown, per_local, per_max, trips_main = timed_lm()
+    elapsed, outs, breakdown, per_local, per_max, trips_main = timed_lm()
+    X = outs[0]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"X": outs[0], "F0": outs[1], "FOpt": outs[2]})
     err = float(np.max(np.abs(X - obj.xstar)) / np.max(np.abs(obj.xstar)))
     rows_extra = None
-    if world > 1:
+    if world > 1 and args.full:
         # rows mode beside the headline (labelled extra; linear residuals only): every rank the
         # same environment, LevMarqMPI reads it once per solve and checks that the ranks agree
         os.environ["PNOL_LM_FD"] = "rows"
-        el_r, X_r, _, pl_r, pm_r, tr_r = timed_lm()
+        el_r, (X_r, _, _), _, pl_r, pm_r, tr_r = timed_lm()
         os.environ.pop("PNOL_LM_FD", None)
         rows_extra = {
             "value": args.steps / el_r, "unit": "iters/s", "ms_per_step": el_r / args.steps * 1e3,
@@ -643,15 +675,15 @@ def main():
     trips[:] = trips_main
 
     hg_sharded = None
-    if world > 1 and not args.no_hg:
+    if world > 1 and args.full and not args.no_hg:
         hg_sharded = bench_hg_sharded(dctx, HG_N, world, rank)
     hg = None
-    if rank == 0 and not args.no_hg:
+    if rank == 0 and args.full and not args.no_hg:
         hg = bench_hg(ctx, HG_N)
         hg4096 = bench_hg(ctx, 4096)
         hg16384 = bench_hg(ctx, 16384)      # cfg 5: D = 2.15 GB
     bfgs2 = bnd5 = None
-    if rank == 0 and not args.no_bfgs:
+    if rank == 0 and args.full and not args.no_bfgs:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         bfgs2 = bench_bfgs_solve(ctx, 0, 4096, 1.0, CFG2_P)
         n5 = 16384
@@ -727,7 +759,7 @@ def main():
                                                   {}).get("traffic_bytes_per_launch"),
                                "n": HG_N}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(m, n)
         ms_per_step = elapsed / args.steps * 1e3
         if world > 1:
@@ -742,7 +774,7 @@ def main():
             "metric": f"LM iters/sec at m={m},n={n}",
             "value": args.steps / elapsed,
             "unit": "iters/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "strong",

@@ -5,7 +5,7 @@ set -u
 T=${TAG:-r06}
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-bfgs"
+B="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-bfgs"
 run() { local name=$1; shift; timeout -s KILL 300 "$@" > gpurun_out/$name.log 2>&1; local rc=$?; echo "$name rc=$rc"; return $rc; }
 SQ="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
 MF="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_LDS SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE"

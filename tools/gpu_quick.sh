@@ -14,6 +14,7 @@ if [ -n "$K" ]; then
   ok $rc || exit $rc
 fi
 if [ "${BENCH:-0}" = "1" ]; then
+  BENCH_ARGS="--full ${BENCH_ARGS:-}"   # the whole line: the BFGS blocks and the CPU baseline beside the LM steps
   timeout -k 10 ${BENCH_LIMIT:-600} python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.json 2> gpurun_out/bench.err
   rc=$?; echo "bench rc=$rc"; tail -c 4000 gpurun_out/bench.json; tail -5 gpurun_out/bench.err
   ok $rc || exit $rc

@@ -6,7 +6,7 @@ set -u
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 for n in ${NS:-2 4 8}; do
-  timeout -k 10 400 python bench.py --gpus $n --host-comm --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-bfgs \
+  timeout -k 10 400 python bench.py --gpus $n --host-comm --full --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-bfgs \
       > gpurun_out/bench_hostcomm$n.json 2> gpurun_out/bench_hostcomm$n.err
   rc=$?; echo "hostcomm$n rc=$rc"; tail -c 400 gpurun_out/bench_hostcomm$n.json; echo
   [ "$rc" -eq 0 ] || exit $rc
