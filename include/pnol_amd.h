@@ -81,13 +81,19 @@ int pnol_memcpy_d2h(pnol_ctx* ctx, void* dst, const void* src, size_t bytes);  /
 /* ---- BFGS dense inverse Hessian ------------------------------------------------------ */
 /* p = -D g.  Replaces matrixVectorMultiply(D, dFdX, p) + negate, BFGS_with_linesearch.cpp:78-79
  * (also BFGS_with_linesearch_MPI.cpp:81-82, BFGS_bnd_linesearch.cpp:142-143).
- * D is n x n row-major with leading dimension ldd (doubles, even, 16-byte aligned base).
- * n <= PNOL_SEQ_MAX uses reference summation order (bitwise equal to the CPU path). */
+ * D is n x n row-major with leading dimension ldd >= n (doubles).
+ * n <= PNOL_SEQ_MAX uses reference summation order (bitwise equal to the CPU path).
+ * Alignment: D, g and p need only a double's 8 bytes and ldd may be odd.  The streaming kernel
+ * (16-byte loads) runs when D and g are 16-byte aligned and ldd is even; otherwise a slower
+ * 8-byte-load kernel computes the product (its sums are grouped differently: equal within the
+ * rounding of a reordered fp64 sum, not bitwise).  Nothing is refused for alignment. */
 #define PNOL_SEQ_MAX 64
 /* columns per FD point tile (the FD GEMM's point-tile width, the multi-GPU split unit) */
 #define PNOL_FD_TILE 128
 int pnol_hg_d(pnol_ctx* ctx, const double* D, int ldd, const double* g, double* p, int n);
-/* y = -A x for a rows x cols row-major A (the same streaming kernel; also rhs = -J^T F). */
+/* y = -A x for a rows x cols row-major A (the same streaming kernel at every size, no
+ * reference-order form).  Alignment as pnol_hg_d: A, x, y 8-byte aligned, lda >= cols of either
+ * parity; A and x 16-byte aligned with an even lda select the 16-byte-load kernel. */
 int pnol_gemv_neg_d(pnol_ctx* ctx, const double* A, int lda, int rows, int cols, const double* x, double* y);
 
 /* D <- (I - rho s y^T) D (I - rho y s^T) + rho s s^T, rho = 1/(y.s), in the reference's
@@ -149,7 +155,11 @@ int pnol_gather_submatrix_mpi_d(pnol_ctx* ctx, const double* D, int ldd, int n, 
  * Replaces matrixTranspose + matrixMultiply(JT, J, JTJ) + the diag loop,
  * LevenbergMarquardt.cpp:59-73.  JT is n x m row-major (ld ldjt): column j of J is row j.
  * fp64 MFMA (v_mfma_f64_16x16x4_f64) SYRK on the lower triangle, mirrored; n <= PNOL_SEQ_MAX
- * and m <= 4096 use the reference summation order.  jtj_diag (nullable) receives (J^T J)_ii. */
+ * and m <= 4096 use the reference summation order.  jtj_diag (nullable) receives (J^T J)_ii.
+ * Alignment: JT, A and jtj_diag need only a double's 8 bytes; ldjt >= m and lda >= n may be odd.
+ * An even ldjt selects 16-byte loads of JT (issued at whatever 8-byte address the rows start at),
+ * an odd one 8-byte loads; the sums and their order are the same, so A is bitwise the same for
+ * every ldjt, lda and base address.  Only columns < n of A's rows are written. */
 int pnol_jtj_d(pnol_ctx* ctx, const double* JT, int ldjt, int m, int n, double lambda,
                double* A, int lda, double* jtj_diag);
 /* LevMarqMPI's J^T J (LevenbergMarquardtMPI.cpp:64-78, replicated on every rank in the
@@ -214,7 +224,12 @@ int pnol_lm_normal_unpack_mpi_d(pnol_ctx* ctx, int m, int n, double lambda, doub
  * acting on dinfo[1] keeps every rank on the same branch and the same collectives.  One rank or
  * no communicator: dinfo[1] = the code of dinfo[0]. */
 int pnol_lm_agree_status_d(pnol_ctx* ctx, int* dinfo);
-/* rhs = -(J^T F), LevenbergMarquardt.cpp:78-80 */
+/* rhs = -(J^T F), LevenbergMarquardt.cpp:78-80 (n <= PNOL_SEQ_MAX and m <= 4096: the reference
+ * summation order; otherwise one partial per m-slice and the slice tree of pnol_jtj_d).
+ * Alignment: JT, F and rhs need only a double's 8 bytes and ldjt >= m may be odd.  JT's rows are
+ * read with 16-byte loads when JT is 16-byte aligned and ldjt even, F with 16-byte loads when F is
+ * 16-byte aligned, with 8-byte loads otherwise; each lane multiplies the same pairs in the same
+ * order either way, so rhs is bitwise the same for every alignment. */
 int pnol_jtr_d(pnol_ctx* ctx, const double* JT, int ldjt, int m, int n, const double* F, double* rhs);
 /* sigma = A^{-1} rhs, replacing luSolve(A, rhs, sigma), LevenbergMarquardt.cpp:83.
  * method 0 = auto (n <= PNOL_SEQ_MAX: reference LU; else the tile Cholesky, LU on a non-positive

@@ -133,8 +133,9 @@ __global__ __launch_bounds__(256) void k_gemv_neg(const double* __restrict__ A, 
 // fewer concurrent DRAM streams open than with a wave per row.  NT: non-temporal loads
 // (D is streamed once; keep it out of L2 / MALL).  Partial sums are combined in a fixed
 // order through LDS.
-// VEC = false: the same arithmetic with 8-byte loads (rows not 16-byte aligned)
-template <int R, bool NT, bool VEC = true>
+// VEC = false: the same arithmetic with 8-byte loads (rows not 16-byte aligned); XV = false: the
+// same for x (x 8-byte but not 16-byte aligned).  Each lane multiplies the same pairs either way.
+template <int R, bool NT, bool VEC = true, bool XV = true>
 __device__ __forceinline__ void gemv_neg_wg_body(const double* __restrict__ A, long lda, int rows, int cols,
                                                  const double* __restrict__ x, double* __restrict__ y) {
     __shared__ double part[4][R];
@@ -153,6 +154,7 @@ __device__ __forceinline__ void gemv_neg_wg_body(const double* __restrict__ A, l
     const int pairs = cols >> 1;
     constexpr int SC = kU * kWave;
     const int nfull = pairs / SC;
+    auto ld8 = [](const double* q) -> double2 { return make_double2(q[0], q[1]); };   // two 8-byte loads
     auto ld = [&](const double* q) -> double2 {
         if (!VEC) return make_double2(q[0], q[1]);
         const double2* p = reinterpret_cast<const double2*>(q);
@@ -168,7 +170,10 @@ __device__ __forceinline__ void gemv_neg_wg_body(const double* __restrict__ A, l
     if (sc < nfull) {
         double2 cur[R][kU], curx[kU];
 #pragma unroll
-        for (int u = 0; u < kU; ++u) curx[u] = xv[sc * SC + u * kWave + lane];
+        for (int u = 0; u < kU; ++u) {
+            if constexpr (XV) curx[u] = xv[sc * SC + u * kWave + lane];
+            else curx[u] = ld8(x + 2 * (sc * SC + u * kWave + lane));
+        }
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -176,7 +181,10 @@ __device__ __forceinline__ void gemv_neg_wg_body(const double* __restrict__ A, l
         for (sc += 4; sc < nfull; sc += 4) {
             double2 nxt[R][kU], nxtx[kU];
 #pragma unroll
-            for (int u = 0; u < kU; ++u) nxtx[u] = xv[sc * SC + u * kWave + lane];
+            for (int u = 0; u < kU; ++u) {
+                if constexpr (XV) nxtx[u] = xv[sc * SC + u * kWave + lane];
+                else nxtx[u] = ld8(x + 2 * (sc * SC + u * kWave + lane));
+            }
 #pragma unroll
             for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -193,7 +201,9 @@ __device__ __forceinline__ void gemv_neg_wg_body(const double* __restrict__ A, l
     }
     if (wave == 0) {
         for (int c = nfull * SC + lane; c < pairs; c += kWave) {
-            double2 xr = xv[c];
+            double2 xr;
+            if constexpr (XV) xr = xv[c];
+            else xr = ld8(x + 2 * c);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 double2 a = VEC ? reinterpret_cast<const double2*>(arow[r])[c]
@@ -231,14 +241,14 @@ __global__ __launch_bounds__(256) void k_gemv_neg_wg(const double* __restrict__ 
 
 // -J^T F per m-slice (LevMarq / LevMarqMPI, syrk.hip): blockIdx.y = slice s0 + y of J^T (at
 // A + s * sstride, row stride lda) against F[s mS, (s + 1) mS) -> y[blockIdx.y * rows + j].
-template <int R, bool VEC>
+template <int R, bool VEC, bool XV>
 __global__ __launch_bounds__(256) void k_gemv_neg_slices(const double* __restrict__ A, long lda, long sstride, int rows,
                                                          int m, int mS, int s0, const double* __restrict__ x,
                                                          double* __restrict__ y) {
     const int s = s0 + blockIdx.y;
     const int cols = max(0, min(mS, m - s * mS));
-    gemv_neg_wg_body<R, true, VEC>(A + (long)s * sstride, lda, rows, cols, x + (long)s * mS,
-                                   y + (long)blockIdx.y * rows);
+    gemv_neg_wg_body<R, true, VEC, XV>(A + (long)s * sstride, lda, rows, cols, x + (long)s * mS,
+                                       y + (long)blockIdx.y * rows);
 }
 
 // any lda / alignment: one wave per row, 8-byte loads, 4 in flight per lane
@@ -469,7 +479,11 @@ __global__ __launch_bounds__(256) void k_bfgs_pass(double* __restrict__ Dsh, lon
             if (!c1ok) { e1 = o1; }
             if (WB && r0 + q < r_end && c0ok) {
                 double* dst = D + (long)(r0 + q) * ldd + col;
-                if (VEC) {
+                if (VEC && IDS && !c1ok) {
+                    // column n is padding: the loaded pair's half goes back unchanged below, but a
+                    // synthesised pair has nothing of the buffer's to put there -- leave it alone
+                    __builtin_nontemporal_store(e0, dst);
+                } else if (VEC) {
                     __builtin_nontemporal_store(e0, dst);
                     __builtin_nontemporal_store(c1ok ? e1 : cur[q].y, dst + 1);
                 } else {
@@ -619,7 +633,7 @@ int launch_gemv_neg(pnol_ctx* ctx, const double* A, int lda, int rows, int cols,
 int launch_gemv_neg_slices(pnol_ctx* ctx, const double* A, int lda, long sstride, int rows, int m, int mS, int s0,
                            int nsl, const double* x, double* y, hipStream_t stream) {
     if (!stream) stream = ctx->stream;
-    if (!A || !x || !y || rows <= 0 || nsl <= 0 || (mS & 1) || !aligned16(x)) return PNOL_ERR_ARG;
+    if (!A || !x || !y || rows <= 0 || nsl <= 0 || (mS & 1)) return PNOL_ERR_ARG;
     // rows per workgroup (PNOL_JTR_ROWS = 1, 2 or 4; tuning -- each row's sum is the same for all)
     static const int R = [] {
         const char* e = std::getenv("PNOL_JTR_ROWS");
@@ -628,14 +642,19 @@ int launch_gemv_neg_slices(pnol_ctx* ctx, const double* A, int lda, long sstride
     }();
     // 16-byte row loads when every row start is 16-byte aligned; the same sums otherwise
     const bool vec = !((lda & 1) || (sstride & 1) || !aligned16(A));
+    // the same for x: every slice starts an even number of doubles past x (mS is even)
+    const bool xvec = aligned16(x);
     const dim3 grid((rows + R - 1) / R, nsl);
-#define PNOL_SLICES(RR, V) \
-    hipLaunchKernelGGL((k_gemv_neg_slices<RR, V>), grid, dim3(256), 0, stream, A, (long)lda, sstride, rows, m, mS, s0, x, y)
-    if (vec) {
-        if (R == 1) PNOL_SLICES(1, true); else if (R == 4) PNOL_SLICES(4, true); else PNOL_SLICES(2, true);
-    } else {
-        if (R == 1) PNOL_SLICES(1, false); else if (R == 4) PNOL_SLICES(4, false); else PNOL_SLICES(2, false);
-    }
+#define PNOL_SLICES(RR, V, XV)                                                                                      \
+    hipLaunchKernelGGL((k_gemv_neg_slices<RR, V, XV>), grid, dim3(256), 0, stream, A, (long)lda, sstride, rows, m, mS, \
+                       s0, x, y)
+#define PNOL_SLICES_R(V, XV) \
+    do { if (R == 1) PNOL_SLICES(1, V, XV); else if (R == 4) PNOL_SLICES(4, V, XV); else PNOL_SLICES(2, V, XV); } while (0)
+    if (vec && xvec) PNOL_SLICES_R(true, true);
+    else if (xvec) PNOL_SLICES_R(false, true);
+    else if (vec) PNOL_SLICES_R(true, false);
+    else PNOL_SLICES_R(false, false);
+#undef PNOL_SLICES_R
 #undef PNOL_SLICES
     return launch_check();
 }
