@@ -22,6 +22,7 @@
 // the LU -- a timeout is a scheduling event, not a property of A.
 #include "../pnol_internal.hpp"
 #include "../pnol_comm.hpp"
+#include "../chol_tasks.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -916,8 +917,12 @@ __device__ unsigned long long g_chol_la[64 * 4];
     if (threadIdx.x == 128 && (d) < 64) g_chol_la[4 * (d) + (i)] = __builtin_amdgcn_s_memtime();
 #define PNOL_CRIT(k, i) \
     if (threadIdx.x == 0 && (k) >= 0 && (k) < 64) g_chol_crit[8 * (k) + (i)] = __builtin_amdgcn_s_memrealtime();
-#define PNOL_CHOL_STAMP(k, i) \
-    if (threadIdx.x == 0 && (k) + 1 < 64) g_chol_clk[8 * ((k) + 1) + (i)] = __builtin_amdgcn_s_memtime();
+#define PNOL_CRIT_IF(c, k, i) \
+    if (c) { PNOL_CRIT(k, i) }
+// slot i of step k's g_chol_clk row: a value, or the shader clock now
+#define PNOL_CHOL_CLK_PUT(k, i, v) \
+    if (threadIdx.x == 0 && (k) + 1 < 64) g_chol_clk[8 * ((k) + 1) + (i)] = (v);
+#define PNOL_CHOL_STAMP(k, i) PNOL_CHOL_CLK_PUT(k, i, __builtin_amdgcn_s_memtime())
 __device__ __forceinline__ void chol_tl_mark(int k, int cls, unsigned long long t0) {
     if (threadIdx.x == 0 && k + 1 < 64) {
         const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
@@ -925,10 +930,27 @@ __device__ __forceinline__ void chol_tl_mark(int k, int cls, unsigned long long 
         atomicMax(&g_chol_tl[((k + 1) * 3 + cls) * 2 + 1], t1);
     }
 }
+// A timed scope (a launch's workgroup, a chain step, a worker task): PNOL_TL_BEGIN declares its
+// start stamps, PNOL_TL_MARK folds start and now into g_chol_tl's class cls, PNOL_TL_DIAG_END is
+// the diagonal workgroup's close (class 0, its start clock in slot 0, its end clock in slot 7;
+// PNOL_TL_BARRIER: all its waves are done).  The scopes' own variables: a kernel body holds no
+// preprocessor conditional.
+#define PNOL_TL_BEGIN() const unsigned long long tl0_ = __builtin_amdgcn_s_memrealtime();
+#define PNOL_TL_BEGIN_CLK() PNOL_TL_BEGIN() const unsigned long long ck0_ = __builtin_amdgcn_s_memtime();
+#define PNOL_TL_MARK(k, cls) chol_tl_mark(k, cls, tl0_);
+#define PNOL_TL_BARRIER() __syncthreads();
+#define PNOL_TL_DIAG_END(k) PNOL_TL_MARK(k, 0) PNOL_CHOL_CLK_PUT(k, 0, ck0_) PNOL_CHOL_STAMP(k, 7)
 #else
+#define PNOL_CHOL_CLK_PUT(k, i, v)
 #define PNOL_CHOL_STAMP(k, i)
 #define PNOL_CRIT(k, i)
+#define PNOL_CRIT_IF(c, k, i)
 #define PNOL_LA_STAMP(d, i)
+#define PNOL_TL_BEGIN()
+#define PNOL_TL_BEGIN_CLK()
+#define PNOL_TL_MARK(k, cls)
+#define PNOL_TL_BARRIER()
+#define PNOL_TL_DIAG_END(k)
 #endif
 #ifdef PNOL_CHOL_TASKTRACE
 // tools/microbench/chol_tasktrace.hip: per worker task (claim index g) the claim, the end of its
@@ -1284,9 +1306,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_step(double* __restrict__ P, do
     __shared__ int cnt[6];   // diagonal-tile phase words (factor_diag)
     __shared__ int ok_sh;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), wr = wave >> 1, wc = wave & 1;
-#ifdef PNOL_CHOL_TIMELINE
-    const unsigned long long tl0 = __builtin_amdgcn_s_memrealtime(), ck0 = __builtin_amdgcn_s_memtime();
-#endif
+    PNOL_TL_BEGIN_CLK()
     if (k < 0 && blockIdx.x > 0) {   // prep: rows b-1, b-1+G, ... of P
         const int N = T * NB, G = gridDim.x - 1;
         // 16-byte loads and stores, all of a row's loads issued before its stores (N is a multiple
@@ -1354,12 +1374,8 @@ __global__ __launch_bounds__(256, 2) void k_chol_step(double* __restrict__ P, do
         PNOL_CHOL_STAMP(k, 3)
         factor_diag(L, rinv, cnt, W + (long)d * NB * NB, d, info);
         PNOL_CHOL_STAMP(k, 4)
-#ifdef PNOL_CHOL_TIMELINE
-        __syncthreads();
-        chol_tl_mark(k, 0, tl0);
-        if (threadIdx.x == 0 && k + 1 < 64) g_chol_clk[8 * (k + 1)] = ck0;
-        PNOL_CHOL_STAMP(k, 7)
-#endif
+        PNOL_TL_BARRIER()
+        PNOL_TL_DIAG_END(k)
         return;
     }
 
@@ -1397,9 +1413,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_step(double* __restrict__ P, do
             bv[i0 + t] -= s;
             if (b == 1) zv[k0 + t] = zsh[t];
         }
-#ifdef PNOL_CHOL_TIMELINE
-        chol_tl_mark(k, 1, tl0);
-#endif
+        PNOL_TL_MARK(k, 1)
         return;
     }
 
@@ -1427,9 +1441,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_step(double* __restrict__ P, do
     __syncthreads();
     mfma_xyt<true>(acc, X, i != j ? Y : X, wr, wc, lane);
     acc_store(acc, P, ldp, i * NB, j * NB, wr, wc, lane);
-#ifdef PNOL_CHOL_TIMELINE
-    chol_tl_mark(k, 2, tl0);
-#endif
+    PNOL_TL_MARK(k, 2)
 }
 
 // ---- the persistent form (method 5) --------------------------------------------------------
@@ -1438,13 +1450,15 @@ __global__ __launch_bounds__(256, 2) void k_chol_step(double* __restrict__ P, do
 //   blockIdx 0     the diagonal chain: for d = 1 .. T-1, once tiles (d, d-1) and (d, d) hold
 //                  the updates of columns < d-1, diag_prepare + factor_diag -> W_d, published;
 //                  no launch boundary and no wait for the rest of step d-1's work;
-//   blockIdx >= 1  workers taking tasks from an atomic counter (task_of's order) -- step k's
+//   blockIdx >= 1  workers taking tasks from an atomic counter (task_of's order,
+//                  ../chol_tasks.hpp) -- step k's
 //                  panel rows i = k+1 .. T-1 and its update tiles by columns (the same task set as
-//                  the blocks of launch k), each step's four critical tasks handed out one step
+//                  the blocks of launch k), each step's critical set of tasks handed out one step
 //                  early -- each waiting on the diagonal chain (which itself waits only on tasks of
-//                  steps <= d-2) or on tasks handed out before it, except that the <= 4 early
+//                  steps <= d-2) or on tasks handed out before it, except that the early
 //                  tasks may wait on their predecessor step's later tasks: the queue drains once
-//                  5 workers are resident (order 0, PNOL_CHOL_ORDER=0: with any number).
+//                  more workers than one critical set has tasks are resident (chol_claim_order;
+//                  order 0, PNOL_CHOL_ORDER=0: with any number).
 // Progress words (int, zeroed by the prep): wdone[d] (W_d published), lcnt[i] (panels of row i
 // stored in Lm), bcnt[i] (forward-substitution updates applied to b_i), ver[i * T + j] (update
 // steps applied to tile (i, j)); plus the task counter.  Hand-offs without fences: every byte
@@ -1518,8 +1532,8 @@ struct RedArgs {
     // the matrix and b already in P / bv (a reduce launch wrote them; every version and b word
     // starts at 0): no reduce tasks, the chain factors tile 0 itself
     bool preloaded = false;
-    // the worker claim order (task_of): 1 (default) each step's critical tasks one step early,
-    // 0 by step (PNOL_CHOL_ORDER=0)
+    // the worker claim order (task_of, ../chol_tasks.hpp): 1 (default) each step's critical tasks
+    // one step early, 0 by step (PNOL_CHOL_ORDER=0)
     int order = 1;
     // the two critical update tasks of each step form their L panels themselves
     // (PNOL_CHOL_SELFL=0: they wait for the panel tasks' stored L)
@@ -1621,86 +1635,50 @@ __device__ void red_task(int u, const RedArgs& red, double* __restrict__ P, long
     publish(pw.ver + I * T + J, 0);
 }
 
+// The workers' claim order -- claim index g -> step k and a panel row or an update tile (Task,
+// task_of), the task counts and the worker guard (chol_claim_order) -- is ../chol_tasks.hpp,
+// shared with the launcher and with the host program that tests/test_chol_claim_order.py proves
+// the order's permutation and liveness properties on.
 
-// The workers' claim order: claim index g -> step k and task -- a panel row i (L_ik, b_i), or
-// an update tile (i, j) -= L_ik L_jk^T.  Step k (R = T-1-k panel rows) holds
-// S_k = R + R (R + 1) / 2 - 1 tasks, local index l: panels l < R, then the update tiles in
-// column order with the two the chain needs next first (l = R: (k+2, k+1), l = R+1: (k+2, k+2)).
-//   order 0: step by step (every task waits only on tasks claimed before it).
-//   order 1: each step's critical set C_k (l in {0, 1, R, R+1}; {0} for R = 1) one step early:
-//            C_0, C_1, rest_0, C_2, rest_1, ..., C_{T-2}, rest_{T-3}, rest_{T-2}.  A task of C_{k+1}
-//            may wait on a task of rest_k claimed after it: up to 4 workers can wait on unclaimed
-//            tasks, so this order needs more than 4 workers.
-// (By tile column -- all of a column's updates before the next column's panels, every
-// dependency claimed first -- measured 1.23 ms per solve against 0.60: the workers pile up on
-// far-column tasks waiting for the chain while runnable updates stay unclaimed.)
-// Order 1 against order 0: 6 of 6 same-box bench pairs faster, +0.5-1% LM iters/s.
-struct Task {
-    int k, i, j;   // j < 0: panel row i of step k
-    int h;         // >= 0: the 32-row half h of a split critical update
-};
-// split: the two critical updates (l = R, R + 1) are four half tasks (l = R .. R + 3), the other
-// updates one index later by two.  rowmajor: the updates after the critical two by tile row
-// (rows k+3, k+4, ..., each from column k+1 to the diagonal) instead of by tile column: the chain
-// needs row d's tiles at step d - 1, so the rows near the diagonal come first.
-__device__ __forceinline__ Task task_local(int k, int l, int T, bool split, bool rowmajor = false) {
-    const int R = T - 1 - k;
-    if (l < R) return {k, k + 1 + l, -1, -1};
-    int q = l - R;
-    if (split && R >= 2) {
-        if (q < 4) return {k, k + 2, q < 2 ? k + 1 : k + 2, q & 1};
-        q -= 2;
-    }
-    if (rowmajor && q >= 2) {
-        int r = q - 2, i = k + 3;   // row i holds the tiles (i, k+1) .. (i, i): i - k of them
-        while (r >= i - k) {
-            r -= i - k;
-            ++i;
-        }
-        return {k, i, k + 1 + r, -1};
-    }
-    // full column order f: column k+1 holds f = 0 .. R-1 (f = 0 is the chain's), column k+2
-    // starts at f = R, ...
-    int u = q == 0 ? 1 : (q == 1 ? R : (q < R ? q : q + 1));
-    int j = k + 1;
-    while (u >= T - j) {
-        u -= T - j;
-        ++j;
-    }
-    return {k, j + u, j, -1};
+// lane 0 of a worker: wait until W_k is published (w0_prep: tile 0 was factored by the prep
+// launch, so W_0 is there before this launch starts and has no word)
+__device__ __forceinline__ bool wait_w(const PersistWords pw, int k, bool w0_prep, int* info) {
+    return (k == 0 && w0_prep) || spin_ge(pw.wdone + k, 1, info);
 }
-// tasks of step k (R = T - 1 - k panel rows), with the split critical updates
-__host__ __device__ __forceinline__ int step_tasks(int R, bool split) {
-    return R + R * (R + 1) / 2 - 1 + (split && R >= 2 ? 2 : 0);
+
+// The prologue of a critical update (i, j) of step k that forms its L panels itself, whole tile
+// or half, in two parts with the task's own accumulator loads between them (issued before the
+// staging, so they stay in flight across the wait for the chain):
+//   selfl_wait_tiles  the tile and A_ik, A_jk hold the updates through column k - 1
+//   selfl_stage       A_ik into X and A_jk into Z (i != j) while lane 0 waits for W_k, then W_k
+//                     into Y; its last barrier ends the staging
+// False: a wait failed (*info is set) and the workgroup leaves.  ok_sh is the kernel's shared
+// word: each write here is a barrier behind the previous read, and the caller's next write is
+// behind selfl_stage's last barrier.  stamp: this task records the critical-path trace's
+// "flags ok" time.
+// (As one function taking the loads as a callable, the whole-tile task compiled to 16 more
+// AGPRs; in this form the kernel's register, scratch and LDS counts are unchanged.)
+__device__ __forceinline__ bool selfl_wait_tiles(int T, const PersistWords pw, int i, int j, int k, int& ok_sh,
+                                                 int* info) {
+    if (threadIdx.x == 0)
+        ok_sh = spin_all<3>({pw.ver + i * T + j, pw.ver + i * T + k, pw.ver + j * T + k}, {k, k, k}, info);
+    __syncthreads();
+    return ok_sh;
 }
-__device__ __forceinline__ Task task_of(int g, int T, int order, bool split, bool rowmajor = false) {
-    if (order == 1) {
-        const int nc = split ? 6 : 4;   // the critical set: panels k+1, k+2 and the updates (halves)
-        auto csz = [&](int kk) { return T - 1 - kk >= 2 ? nc : 1; };
-        auto cmap = [&](int x, int RR) { return x < 2 ? x : RR + x - 2; };
-        if (g < csz(0)) return task_local(0, cmap(g, T - 1), T, split, rowmajor);
-        g -= csz(0);
-        for (int kk = 0;; ++kk) {
-            if (kk + 1 <= T - 2) {
-                const int c1 = csz(kk + 1);
-                if (g < c1) return task_local(kk + 1, cmap(g, T - 2 - kk), T, split, rowmajor);
-                g -= c1;
-            }
-            const int RR = T - 1 - kk, S = step_tasks(RR, split), rest = S - csz(kk);
-            if (g < rest || kk >= T - 2)
-                return task_local(kk, g < RR - 2 ? g + 2 : g + (split && RR >= 2 ? 6 : 4), T, split, rowmajor);
-            g -= rest;
-        }
-    }
-    int k = 0, R = T - 1;
-    for (;;) {
-        const int S = step_tasks(R, split);
-        if (g < S || R <= 1) break;
-        g -= S;
-        ++k;
-        --R;
-    }
-    return task_local(k, g, T, split, rowmajor);
+__device__ __forceinline__ bool selfl_stage(const double* __restrict__ P, long ldp, const double* __restrict__ W,
+                                            const PersistWords pw, int i, int j, int k, bool w0_prep,
+                                            double* __restrict__ X, double* __restrict__ Y, double* __restrict__ Z,
+                                            int& ok_sh, int* info, [[maybe_unused]] bool stamp) {
+    const int k0 = k * NB;
+    stage_tile<true>(X, P, ldp, i * NB, k0);
+    if (i != j) stage_tile<true>(Z, P, ldp, j * NB, k0);
+    if (threadIdx.x == 0) ok_sh = wait_w(pw, k, w0_prep, info);
+    __syncthreads();
+    if (!ok_sh) return false;
+    PNOL_CRIT_IF(stamp, k, 5)
+    stage_tile<true>(Y, W + (long)k * NB * NB, NB, 0, 0);
+    __syncthreads();
+    return true;
 }
 
 __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P, double* __restrict__ Lm, long ldp,
@@ -1722,16 +1700,16 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
     const PersistWords pw = persist_words(flags, T);
     double* X = smem;
     double* Y = smem + kStage;
+    // tile 0: factored by the prep launch (w0_prep: W_0 is there from the start), or by the chain
+    // once the reduce tasks or a reduce launch have stored it
+    const bool w0_prep = !red.part && !red.packed && !red.preloaded, smode = !w0_prep;
 
     if (blockIdx.x == 0) {   // ---------------- the diagonal chain
         const EarlyLds E{pfx, pll, pfc, ew};
         if (t < 4) ew[t] = 0;
-        const bool smode = red.part || red.packed || red.preloaded;   // the chain also factors tile 0
         for (int d = smode ? 0 : 1; d < T; ++d) {
             const int k = d - 1;
-#ifdef PNOL_CHOL_TIMELINE
-            const unsigned long long tl0 = __builtin_amdgcn_s_memrealtime(), ck0 = __builtin_amdgcn_s_memtime();
-#endif
+            PNOL_TL_BEGIN_CLK()
             if (t == 0) {
                 const bool ok = __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 &&
                                 (d == 0 ? spin_ge(pw.ver, 0, info)
@@ -1745,9 +1723,7 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
             // the previous factor's waves 2 / 3 staged this tile and did half of its products
             const bool pre = lookahead && ew[0] == 1;
             const bool staged = lookahead && ew[0] == 3;   // the tiles only, in pfx / pfc
-#ifdef PNOL_CHOL_TIMELINE
-            if (t == 0 && k + 1 < 64) g_chol_clk[8 * (k + 1) + 6] = pre ? 1 : (staged ? 2 : 0);
-#endif
+            PNOL_CHOL_CLK_PUT(k, 6, pre ? 1 : (staged ? 2 : 0))
             if (d == 0) {   // tile 0 as the reduce tasks stored it (sc1 loads)
                 const int row = t >> 2, c0 = (t & 3) * 16;
                 double v[16];
@@ -1777,16 +1753,15 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
             PNOL_CHOL_STAMP(k, 4)
             publish(pw.wdone + d, 1);   // its barrier also ends every read of this step's LDS
             PNOL_CRIT(d, 0)
-#ifdef PNOL_CHOL_TIMELINE
-            chol_tl_mark(k, 0, tl0);
-            if (threadIdx.x == 0 && k + 1 < 64) g_chol_clk[8 * (k + 1)] = ck0;
-            PNOL_CHOL_STAMP(k, 7)
-#endif
+            PNOL_TL_DIAG_END(k)
         }
         return;
     }
 
-    const int nred = (red.part || red.packed) ? 1 + T * (T + 1) / 2 : 0;   // the reducing form's first tasks
+    const int nred = (red.part || red.packed) ? chol_reduce_task_count(T) : 0;   // the reducing form's first tasks
+    const bool split = red.selfl && red.split;
+    // order 1 holds only with more workers than one critical set has tasks (chol_tasks.hpp)
+    const int order = chol_claim_order(red.order, (int)gridDim.x - 1, split);
     int pre = -1;   // lane 0: the next task, claimed during the last one's publish (publish_claim)
     for (;;) {   // ---------------- workers
         if (t == 0) {
@@ -1803,18 +1778,13 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
         }
         g -= nred;
         PNOL_TASK_T0(g)
-        const bool split = red.selfl && red.split;
-        // order 1 lets each critical set's tasks (4, or 6 split) wait on unclaimed ones: more
-        // workers than that, or step order
-        const Task tk = task_of(g, T, red.order == 1 && gridDim.x <= (split ? 7 : 5) ? 0 : red.order, split, red.rowmajor);
+        const Task tk = task_of(g, T, order, split, red.rowmajor);
         const int k = tk.k;
         const int k0 = k * NB;
         if (tk.j < 0) {   // ---- panel row i: L_ik = A_ik W_k^T, then b_i -= L_ik (W_k b_k)
             const int i = tk.i, i0 = i * NB;
-#ifdef PNOL_CHOL_TIMELINE
-            const unsigned long long tl0 = __builtin_amdgcn_s_memrealtime();
-            if (i == k + 2) PNOL_CRIT(k, 1)
-#endif
+            PNOL_TL_BEGIN()
+            PNOL_CRIT_IF(i == k + 2, k, 1)
             // A_ik through column k-1, b_k complete and b_i's earlier updates: usually long
             // before W_k, so A_ik is staged while the workgroup waits for the diagonal chain
             if (t == 0) ok_sh = spin_all<3>({pw.ver + i * T + k, pw.bcnt + k, pw.bcnt + i}, {k, k, k}, info);
@@ -1822,10 +1792,8 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
             if (!ok_sh) return;
             stage_tile<true>(X, P, ldp, i0, k0);
             if (t == 0) {   // W_k (tile 0 comes from the prep launch)
-                ok_sh = (k == 0 && !red.part && !red.packed && !red.preloaded) || spin_ge(pw.wdone + k, 1, info);
-#ifdef PNOL_CHOL_TIMELINE
-                if (i == k + 2) PNOL_CRIT(k, 2)
-#endif
+                ok_sh = wait_w(pw, k, w0_prep, info);
+                PNOL_CRIT_IF(i == k + 2, k, 2)
             }
             __syncthreads();
             if (!ok_sh) return;
@@ -1836,10 +1804,8 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
             diag_l_strip(acc, X, Y, wave, lane);
             strip_store<true>(acc, Lm, ldp, i0, k0, wave, lane);
             publish(pw.lcnt + i, k + 1);
-#ifdef PNOL_CHOL_TIMELINE
-            if (i == k + 2) PNOL_CRIT(k, 3)
-            if (i == k + 1) PNOL_CRIT(k, 7)
-#endif
+            PNOL_CRIT_IF(i == k + 2, k, 3)
+            PNOL_CRIT_IF(i == k + 1, k, 7)
             strip_to_rows(acc, X, wave, lane);   // X is free (the products finished before the barrier)
             if (t < NB) {
                 double s = 0.0;
@@ -1857,18 +1823,14 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
             }
             publish_claim(pw.bcnt + i, k + 1, pw.counter, pre);
             PNOL_TASK_END(k, 0)
-#ifdef PNOL_CHOL_TIMELINE
-            chol_tl_mark(k, 1, tl0);
-#endif
+            PNOL_TL_MARK(k, 1)
             continue;
         }
         // ---- update tile (i, j) -= L_ik L_jk^T (task_of's order)
         const int i = tk.i, j = tk.j;
-#ifdef PNOL_CHOL_TIMELINE
-        const unsigned long long tl0 = __builtin_amdgcn_s_memrealtime();
-        const bool crit = i == k + 2 && j == k + 1;
-        if (crit) PNOL_CRIT(k, 4)
-#endif
+        PNOL_TL_BEGIN()
+        [[maybe_unused]] const bool crit = i == k + 2 && j == k + 1;   // the critical-path trace's update
+        PNOL_CRIT_IF(crit, k, 4)
         if (tk.h >= 0) {
             // Half h (rows 32 h .. 32 h + 31) of a critical update tile (k+2, k+1) or (k+2, k+2):
             // as the whole-tile task below (L_ik and L_jk formed here from A and W_k), on half the
@@ -1878,27 +1840,15 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
             // is bitwise the same; the second half to finish publishes its version.
             const int h = tk.h, w = wave;
             double* Z = pfx;
-            if (t == 0)
-                ok_sh = spin_all<3>({pw.ver + i * T + j, pw.ver + i * T + k, pw.ver + j * T + k}, {k, k, k}, info);
-            __syncthreads();
-            if (!ok_sh) return;
-            d4 acc[2];
+            d4 acc[2];   // this wave's two 16 x 16 blocks of the half: block rows 2 h, 2 h + 1, block column w
+            if (!selfl_wait_tiles(T, pw, i, j, k, ok_sh, info)) return;
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    acc[mi][r] = ldg<true>(P + (long)(i * NB + (2 * h + mi) * 16 + (lane >> 4) + 4 * r) * ldp + j * NB +
-                                           w * 16 + (lane & 15));
-            stage_tile<true>(X, P, ldp, i * NB, k0);
-            if (i != j) stage_tile<true>(Z, P, ldp, j * NB, k0);
-            if (t == 0) ok_sh = (k == 0 && !red.part && !red.packed && !red.preloaded) || spin_ge(pw.wdone + k, 1, info);
-            __syncthreads();
-            if (!ok_sh) return;
-#ifdef PNOL_CHOL_TIMELINE
-            if (crit && h == 0) PNOL_CRIT(k, 5)
-#endif
-            stage_tile<true>(Y, W + (long)k * NB * NB, NB, 0, 0);
-            __syncthreads();
+                    acc[mi][r] = ldg<true>(P + (long)(i * NB + (2 * h + mi) * 16 + (lane >> 4) + 4 * r) * ldp +
+                                           j * NB + w * 16 + (lane & 15));
+            if (!selfl_stage(P, ldp, W, pw, i, j, k, w0_prep, X, Y, Z, ok_sh, info, crit && h == 0)) return;
             PNOL_TASK_READY()
             if (i != j) {
                 const int s = 2 * h + (w >> 1), j0 = (w & 1) ? 1 : 0, j1 = (w & 1) ? 2 : 3;
@@ -1929,10 +1879,8 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
                               acc[mi][r]);
             publish_half_claim(pw.half + i * T + j, pw.ver + i * T + j, k + 1, pw.counter, pre);
             PNOL_TASK_END(k, 2)
-#ifdef PNOL_CHOL_TIMELINE
-            if (crit) PNOL_CRIT(k, 6)
-            chol_tl_mark(k, 2, tl0);
-#endif
+            PNOL_CRIT_IF(crit, k, 6)
+            PNOL_TL_MARK(k, 2)
             continue;
         }
         if (red.selfl && i == k + 2 && j >= k + 1) {
@@ -1944,22 +1892,10 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
             // substitution).  A_ik, A_jk and the tile are final through column k - 1 long before
             // W_k, so they are staged while the workgroup waits for the chain.
             double* Z = pfx;   // the chain's look-ahead area (unused by workers) holds A_jk / L_jk
-            if (t == 0)
-                ok_sh = spin_all<3>({pw.ver + i * T + j, pw.ver + i * T + k, pw.ver + j * T + k}, {k, k, k}, info);
-            __syncthreads();
-            if (!ok_sh) return;
             d4 acc[2][2];
+            if (!selfl_wait_tiles(T, pw, i, j, k, ok_sh, info)) return;
             acc_load<true>(acc, P, ldp, i * NB, j * NB, wr, wc, lane);
-            stage_tile<true>(X, P, ldp, i * NB, k0);
-            if (i != j) stage_tile<true>(Z, P, ldp, j * NB, k0);
-            if (t == 0) ok_sh = (k == 0 && !red.part && !red.packed && !red.preloaded) || spin_ge(pw.wdone + k, 1, info);
-            __syncthreads();
-            if (!ok_sh) return;
-#ifdef PNOL_CHOL_TIMELINE
-            if (crit) PNOL_CRIT(k, 5)
-#endif
-            stage_tile<true>(Y, W + (long)k * NB * NB, NB, 0, 0);
-            __syncthreads();
+            if (!selfl_stage(P, ldp, W, pw, i, j, k, w0_prep, X, Y, Z, ok_sh, info, crit)) return;
             PNOL_TASK_READY()
             d4 li[4], lj[4];
             diag_l_strip(li, X, Y, wave, lane);
@@ -1972,10 +1908,8 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
             acc_store<true>(acc, P, ldp, i * NB, j * NB, wr, wc, lane);
             publish_claim(pw.ver + i * T + j, k + 1, pw.counter, pre);
             PNOL_TASK_END(k, 3)
-#ifdef PNOL_CHOL_TIMELINE
-            if (crit) PNOL_CRIT(k, 6)
-            chol_tl_mark(k, 2, tl0);
-#endif
+            PNOL_CRIT_IF(crit, k, 6)
+            PNOL_TL_MARK(k, 2)
             continue;
         }
         // the tile's earlier updates first: its loads stay in flight while the workgroup waits
@@ -1995,16 +1929,12 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
             __syncthreads();   // every read of ok_sh above is done
             if (t == 0) {
                 ok_sh = spin_all<2>({pw.lcnt + i, pw.lcnt + j}, {k + 1, k + 1}, info);
-#ifdef PNOL_CHOL_TIMELINE
-                if (crit) PNOL_CRIT(k, 5)
-#endif
+                PNOL_CRIT_IF(crit, k, 5)
             }
             __syncthreads();
             if (!ok_sh) return;
         }
-#ifdef PNOL_CHOL_TIMELINE
-        else if (crit) PNOL_CRIT(k, 5)
-#endif
+        PNOL_CRIT_IF(crit && st0 == 2, k, 5)
         stage_tile<true>(X, Lm, ldp, i * NB, k0);
         if (i != j) stage_tile<true>(Y, Lm, ldp, j * NB, k0);
         __syncthreads();
@@ -2013,10 +1943,8 @@ __global__ __launch_bounds__(256, 1) void k_chol_persist(double* __restrict__ P,
         acc_store<true>(acc, P, ldp, i * NB, j * NB, wr, wc, lane);
         publish_claim(pw.ver + i * T + j, k + 1, pw.counter, pre);
         PNOL_TASK_END(k, 1)
-#ifdef PNOL_CHOL_TIMELINE
-        if (crit) PNOL_CRIT(k, 6)
-        chol_tl_mark(k, 2, tl0);
-#endif
+        PNOL_CRIT_IF(crit, k, 6)
+        PNOL_TL_MARK(k, 2)
     }
 }
 
@@ -2148,18 +2076,20 @@ __global__ void k_flag_info(int* info, int v) { *info = v; }
 // afterwards when a pivot failed or a chain timed out.
 // PNOL_CHOL_PERSIST = 0 / 1 (read per call: the tests switch it) selects the per-step launches
 // (method 4) or the persistent form; `variant` 4 / 5 forces one.
+// a default-on switch of the environment: unset is on, otherwise its integer value != 0
+static bool env_default_on(const char* name) {
+    const char* e = std::getenv(name);
+    return !e || std::atoi(e) != 0;
+}
+
 static bool chol_persistent(int variant) {
     if (variant == 4) return false;
     if (variant == 5) return true;
-    const char* e = std::getenv("PNOL_CHOL_PERSIST");
-    return e ? std::atoi(e) != 0 : true;
+    return env_default_on("PNOL_CHOL_PERSIST");
 }
 
 // PNOL_BWD_GRANULE = 0: the backward solve's flag hand-off instead of granules (read per call)
-static bool bwd_granules() {
-    const char* e = std::getenv("PNOL_BWD_GRANULE");
-    return !e || std::atoi(e) != 0;
-}
+static bool bwd_granules() { return env_default_on("PNOL_BWD_GRANULE"); }
 
 int launch_chol_solve(pnol_ctx* ctx, const double* A, int lda, const double* rhs, double* sigma, int n, int* dinfo,
                       const double* xbase, double* xnext) {
@@ -2215,16 +2145,10 @@ static int chol_ws(pnol_ctx* ctx, int n, bool persist, CholWs& w) {
 static int chol_persist_launch(pnol_ctx* ctx, hipStream_t st, const CholWs& w, int* dinfo, const RedArgs& red) {
     const int T = w.T;
     RedArgs rp = red;
-    {
-        const char* es = std::getenv("PNOL_CHOL_SELFL");   // read per call (A/B, tests)
-        rp.selfl = !es || std::atoi(es) != 0;
-        const char* eh = std::getenv("PNOL_CHOL_SPLIT");
-        rp.split = !eh || std::atoi(eh) != 0;
-        const char* er = std::getenv("PNOL_CHOL_ROWMAJOR");
-        rp.rowmajor = !er || std::atoi(er) != 0;
-    }
-    int ntasks = 0;
-    for (int R = T - 1; R >= 1; --R) ntasks += step_tasks(R, rp.selfl && rp.split);
+    rp.selfl = env_default_on("PNOL_CHOL_SELFL");   // read per call (A/B, tests)
+    rp.split = env_default_on("PNOL_CHOL_SPLIT");
+    rp.rowmajor = env_default_on("PNOL_CHOL_ROWMAJOR");
+    const int ntasks = chol_step_task_count(T, rp.selfl && rp.split);
     // tuning knob (read per call): PNOL_CHOL5_WORKERS = worker workgroups; one per CU
     // (the look-ahead areas already hold the static LDS to one workgroup per CU).
     // PNOL_CHOL_LOOKAHEAD = 0 turns the diagonal chain's look-ahead off (read per call).
@@ -2244,8 +2168,9 @@ static int chol_persist_launch(pnol_ctx* ctx, hipStream_t st, const CholWs& w, i
     // the same (56: 0.562-0.566), profiles/r05_lookahead_sweep.txt.
     const int lookahead = el ? std::max(0, std::atoi(el)) : 48;
     {
-        // order 1 (each step's critical tasks a step early) lets up to four workers wait on tasks
-        // nobody has claimed yet, so it needs more than four workers resident.  A GPU shared by
+        // order 1 (each step's critical tasks a step early) lets a critical set's worth of workers
+        // wait on tasks nobody has claimed yet, so it needs more workers than that resident
+        // (chol_claim_order, ../chol_tasks.hpp, on the launched count).  A GPU shared by
         // several processes may hold fewer (a 4-process run at cfg 3 stalled one trip until the
         // spin cap, profiles/r06_chol_contention_4p_cfg3.json): ranks sharing the GPU over the
         // host backend, and a context that has seen a timed-out wait, claim in step order.
@@ -2254,7 +2179,7 @@ static int chol_persist_launch(pnol_ctx* ctx, hipStream_t st, const CholWs& w, i
     }
     const int slots = std::max(ctx->num_cu, 1) - 1;
     const int want = ew ? std::atoi(ew) : slots;
-    const int nred = (red.part || red.packed) ? 1 + T * (T + 1) / 2 : 0;
+    const int nred = (red.part || red.packed) ? chol_reduce_task_count(T) : 0;
     const int workers = std::max(1, std::min(ntasks + nred, want));
     hipLaunchKernelGGL(k_chol_persist, dim3(1 + workers), dim3(256), 0, st, w.P, w.Lm, w.ldp, T, w.W, w.bv, w.zv, w.pf,
                        ntasks, dinfo, lookahead, rp);
@@ -2355,6 +2280,14 @@ int launch_chol_reducing_start(pnol_ctx* ctx, const CholRed& cr, bool preloaded,
     return launch_check();
 }
 
+// the tail of every reducing-form entry point: the persistent launch, then the backward solve
+// (+ the trial point)
+static int chol_red_run(pnol_ctx* ctx, hipStream_t st, const CholRed& cr, const RedArgs& red, double* sigma,
+                        const double* xbase, double* xnext) {
+    PNOL_CHECK(chol_persist_launch(ctx, st, cr.w, cr.dinfo, red));
+    return chol_bwd_launch(ctx, st, cr.w, cr.n, sigma, cr.dinfo, xbase, xnext, true);
+}
+
 // the persistent factorisation of the matrix a reduce launch left in P (and b in bv), then the
 // backward solve and xnext = xbase + sigma (launch_chol_reducing_start(preloaded) first)
 int launch_chol_preloaded_run(pnol_ctx* ctx, hipStream_t st, const CholRed& cr, double* sigma, const double* xbase,
@@ -2363,8 +2296,7 @@ int launch_chol_preloaded_run(pnol_ctx* ctx, hipStream_t st, const CholRed& cr, 
     RedArgs red;
     red.n = cr.n;
     red.preloaded = true;
-    PNOL_CHECK(chol_persist_launch(ctx, st, cr.w, cr.dinfo, red));
-    return chol_bwd_launch(ctx, st, cr.w, cr.n, sigma, cr.dinfo, xbase, xnext, true);
+    return chol_red_run(ctx, st, cr, red, sigma, xbase, xnext);
 }
 
 int launch_chol_reducing_run(pnol_ctx* ctx, hipStream_t st, const CholRed& cr, const double* part, int sub,
@@ -2378,8 +2310,7 @@ int launch_chol_reducing_run(pnol_ctx* ctx, hipStream_t st, const CholRed& cr, c
     red.lambda = lambda;
     red.jp = jp;
     red.rhs = rhs;
-    PNOL_CHECK(chol_persist_launch(ctx, st, cr.w, cr.dinfo, red));
-    return chol_bwd_launch(ctx, st, cr.w, cr.n, sigma, cr.dinfo, xbase, xnext, true);
+    return chol_red_run(ctx, st, cr, red, sigma, xbase, xnext);
 }
 
 // LevMarqMPI: the same from the allgathered, summed tiles (packed) and the formed rhs
@@ -2394,8 +2325,7 @@ int launch_chol_reducing_run_packed(pnol_ctx* ctx, hipStream_t st, const CholRed
     red.rhs_in = rhs;
     red.n = cr.n;
     red.lambda = lambda;
-    PNOL_CHECK(chol_persist_launch(ctx, st, cr.w, cr.dinfo, red));
-    return chol_bwd_launch(ctx, st, cr.w, cr.n, sigma, cr.dinfo, xbase, xnext, true);
+    return chol_red_run(ctx, st, cr, red, sigma, xbase, xnext);
 }
 
 }  // namespace pnol

@@ -1,81 +1,75 @@
-"""The persistent Cholesky's worker claim order (kernels/chol.hip task_of / task_local) restated
-in Python, and a claim-queue simulation of the persistent launch: workers claim task indices in
-order, each waits until its dependencies are published (the spin waits of k_chol_persist), and
-the diagonal chain steps when its two tiles are ready.  Checks that the claim order is a
-permutation of the step tasks and that every order the library uses drains -- step order with any
-worker count, order 1 with more workers than one critical set holds (4 tasks, 6 with the split
-critical updates; the kernel falls back to step order below that)."""
+"""The persistent Cholesky's worker claim order as the kernel computes it, and a claim-queue
+simulation of the persistent launch.  The order is not restated here: tests/cpp/chol_claim_table.cpp
+includes csrc/chol_tasks.hpp -- the header kernels/chol.hip takes task_of, the task counts and
+the worker guard from -- and prints the claim table g -> (k, i, j, h), which these tests read.
+The simulation models the waits of k_chol_persist: workers claim task indices in order, each
+waits until its dependencies are published (the kernel's spin waits), and the diagonal chain
+steps when its two tiles are ready.  Checks that the claim order is a permutation of the step
+tasks (written here from their definition) and that every order the library uses drains -- step
+order with any worker count, order 1 from the worker count at which the guard
+(chol_claim_order) keeps it; below that the kernel falls back to step order."""
+import os
+import subprocess
+
 import pytest
 
-
-def step_tasks(R, split):
-    return R + R * (R + 1) // 2 - 1 + (2 if split and R >= 2 else 0)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def task_local(k, l, T, split, rowmajor=False):
-    R = T - 1 - k
-    if l < R:
-        return (k, k + 1 + l, -1, -1)
-    q = l - R
-    if split and R >= 2:
-        if q < 4:
-            return (k, k + 2, k + 1 if q < 2 else k + 2, q & 1)
-        q -= 2
-    if rowmajor and q >= 2:
-        r, i = q - 2, k + 3
-        while r >= i - k:
-            r -= i - k
-            i += 1
-        return (k, i, k + 1 + r, -1)
-    u = 1 if q == 0 else (R if q == 1 else (q if q < R else q + 1))
-    j = k + 1
-    while u >= T - j:
-        u -= T - j
-        j += 1
-    return (k, j + u, j, -1)
+class ClaimTables:
+    """One run of chol_claim_table: tables[(T, order, split, rowmajor)] = [(k, i, j, h), ...] by
+    claim index, need[split] = the smallest worker count at which the guard keeps order 1,
+    guard[split][w] = the order used with w workers when order 1 is requested."""
+
+    def __init__(self, text):
+        self.tables, self.need, self.guard = {}, {}, {}
+        lines = iter(text.splitlines())
+        for line in lines:
+            f = line.split()
+            if f[0] == "guard":
+                split = bool(int(f[1]))
+                self.need[split] = int(f[2])
+                self.guard[split] = [int(x) for x in f[3:]]
+            else:
+                assert f[0] == "table", line
+                T, order, split, rowmajor, nt = (int(x) for x in f[1:])
+                self.tables[(T, order, bool(split), bool(rowmajor))] = [
+                    tuple(int(x) for x in next(lines).split()) for _ in range(nt)]
 
 
-def task_of(g, T, order, split, rowmajor=False):
-    if order == 1:
-        nc = 6 if split else 4
-        csz = lambda kk: nc if T - 1 - kk >= 2 else 1
-        cmap = lambda x, RR: x if x < 2 else RR + x - 2
-        if g < csz(0):
-            return task_local(0, cmap(g, T - 1), T, split, rowmajor)
-        g -= csz(0)
-        kk = 0
-        while True:
-            if kk + 1 <= T - 2:
-                c1 = csz(kk + 1)
-                if g < c1:
-                    return task_local(kk + 1, cmap(g, T - 2 - kk), T, split, rowmajor)
-                g -= c1
-            RR = T - 1 - kk
-            S = step_tasks(RR, split)
-            rest = S - csz(kk)
-            if g < rest or kk >= T - 2:
-                return task_local(kk, g + 2 if g < RR - 2 else g + (6 if split and RR >= 2 else 4), T, split, rowmajor)
-            g -= rest
-            kk += 1
-    k, R = 0, T - 1
-    while True:
-        S = step_tasks(R, split)
-        if g < S or R <= 1:
-            break
-        g -= S
-        k += 1
-        R -= 1
-    return task_local(k, g, T, split, rowmajor)
+@pytest.fixture(scope="module")
+def claims(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("chol_claim") / "chol_claim_table")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I",
+                    os.path.join(ROOT, "parallelnonlinearoptimizationlibrary_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cpp", "chol_claim_table.cpp"), "-o", exe], check=True, timeout=120)
+    r = subprocess.run([exe, "2", "35"], capture_output=True, timeout=120)
+    assert r.returncode == 0, (r.stdout + r.stderr).decode()[-2000:]
+    return ClaimTables(r.stdout.decode())
 
 
 def all_tasks(T, split):
-    return [(k, *task_local(k, l, T, split)[1:]) for k in range(T - 1) for l in range(step_tasks(T - 1 - k, split))]
+    """The step tasks by definition: step k's panel rows i = k+1 .. T-1 and its update tiles (i, j),
+    k+1 <= j <= i <= T-1, except the chain's own (k+1, k+1); with the split critical updates (and at
+    least two panel rows) the tiles (k+2, k+1) and (k+2, k+2) as halves 0 and 1."""
+    out = []
+    for k in range(T - 1):
+        out += [(k, i, -1, -1) for i in range(k + 1, T)]
+        for i in range(k + 1, T):
+            for j in range(k + 1, i + 1):
+                if (i, j) == (k + 1, k + 1):
+                    continue
+                if split and T - 1 - k >= 2 and i == k + 2:
+                    out += [(k, i, j, 0), (k, i, j, 1)]
+                else:
+                    out.append((k, i, j, -1))
+    return out
 
 
-def simulate(T, workers, order, split, selfl=True, rowmajor=False):
+def simulate(table, T, workers, selfl=True):
     """True when every task and chain step completes (no state in which every worker waits on a
-    task nobody can run)."""
-    ntasks = sum(step_tasks(R, split) for R in range(T - 1, 0, -1))
+    task nobody can run).  table: the claim order, claim index -> (k, i, j, h)."""
+    ntasks = len(table)
     ver = {(i, j): 0 for i in range(T) for j in range(i + 1)}   # tile versions (steps applied)
     halves = {}
     lcnt = [0] * T   # panel row i's L published through step lcnt - 1
@@ -118,7 +112,7 @@ def simulate(T, workers, order, split, selfl=True, rowmajor=False):
             progress = True
         for w in range(workers):
             if held[w] is None and nxt < ntasks:
-                held[w] = task_of(nxt, T, order, split, rowmajor)
+                held[w] = table[nxt]
                 nxt += 1
                 progress = True
             if held[w] is not None and ready(held[w]):
@@ -132,26 +126,28 @@ def simulate(T, workers, order, split, selfl=True, rowmajor=False):
 
 
 @pytest.mark.parametrize("split,rowmajor", [(False, False), (True, False), (True, True), (False, True)])
-def test_claim_order_is_a_permutation(split, rowmajor):
+def test_claim_order_is_a_permutation(claims, split, rowmajor):
     for T in range(2, 36):
-        nt = sum(step_tasks(R, split) for R in range(T - 1, 0, -1))
+        want = sorted(all_tasks(T, split))
         for order in (0, 1):
-            got = sorted(task_of(g, T, order, split, rowmajor) for g in range(nt))
-            assert got == sorted(all_tasks(T, split)), (T, order)
+            assert sorted(claims.tables[(T, order, split, rowmajor)]) == want, (T, order)
 
 
 @pytest.mark.parametrize("split,rowmajor", [(False, False), (True, False), (True, True), (False, True)])
-def test_claim_orders_drain(split, rowmajor):
-    need = 7 if split else 5   # order 1 needs more workers than one critical set holds
+def test_claim_orders_drain(claims, split, rowmajor):
+    need = claims.need[split]   # order 1 needs more workers than one critical set holds
     for T in (2, 3, 4, 5, 8, 17, 33):
         for workers in (1, 2, 3, need - 1, need, need + 1, 16, 64):
-            assert simulate(T, workers, 0, split, rowmajor=rowmajor), ("step order", T, workers)
+            assert simulate(claims.tables[(T, 0, split, rowmajor)], T, workers), ("step order", T, workers)
             if workers >= need:
-                assert simulate(T, workers, 1, split, rowmajor=rowmajor), ("order 1", T, workers)
+                assert simulate(claims.tables[(T, 1, split, rowmajor)], T, workers), ("order 1", T, workers)
 
 
-def test_order1_needs_the_worker_guard():
-    """The model has teeth: with fewer workers than a critical set's waiting tasks order 1 stalls
-    (why k_chol_persist claims in step order below 6 / 8 workers)."""
-    assert not simulate(8, 3, 1, False)
-    assert not simulate(8, 5, 1, True)
+def test_order1_needs_the_worker_guard(claims):
+    """The model has teeth: with fewer workers than a critical set's waiting tasks order 1 stalls,
+    and those are worker counts at which the kernel's guard (chol_claim_order) claims in step
+    order."""
+    assert not simulate(claims.tables[(8, 1, False, False)], 8, 3)
+    assert not simulate(claims.tables[(8, 1, True, False)], 8, 5)
+    assert claims.guard[False][3] == 0 and claims.need[False] > 3
+    assert claims.guard[True][5] == 0 and claims.need[True] > 5

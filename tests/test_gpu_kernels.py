@@ -352,7 +352,7 @@ def test_cholesky_persistent_equals_per_step_launches(ctx, n):
     assert np.linalg.norm(_np(s5) - x) <= 1e-10 * np.linalg.norm(x) * np.linalg.cond(A)
 
 
-@pytest.mark.parametrize("n", [130, 1000, 2048])
+@pytest.mark.parametrize("n", [65, 130, 192, 1000, 2048])   # 65: one step, no split tasks; 192: the first half tasks
 def test_cholesky_step_order_claims_bitwise(ctx, monkeypatch, n):
     """The persistent Cholesky's workers in step order (order 0: what a shared GPU and a context
     that saw a timed-out wait use) perform the same tile operations as the default order 1, with
