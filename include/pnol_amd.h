@@ -54,7 +54,7 @@ int pnol_default_ctx(pnol_ctx** out);
 
 /* Per-kernel HIP-event timers on the context's stream (off by default).  Names: "fd_jacobian",
  * "fd_ckpt", "fd_gradient", "linres_eval", "syrk", "syrk_reduce", "jtr", "solve", "hg",
- * "bfgs_pass", "allgather", "exchange_J", "exchange_A".  total_ms sums the recorded launches
+ * "bfgs_pass", "allgather", "exchange_J", "exchange_A", "lm_batch".  total_ms sums the recorded launches
  * since the last reset.  on = 2 times only "fd_jacobian", "fd_ckpt", "syrk", "exchange_J",
  * "allgather", "hg" and "bfgs_pass" (fewer event records between launches). */
 int pnol_ctx_enable_timers(pnol_ctx* ctx, int on);
@@ -341,6 +341,37 @@ int pnol_lm_trip_normal_d(pnol_ctx* ctx, int m, int n, double lambda, double* A,
  * PNOL_FD_TILE), column c written to JT + c * ldjt; one base-chain pass for all tiles. */
 int pnol_fd_jacobian_tiles_d(pnol_ctx* ctx, pnol_dobj* obj, const double* x, const double* h, const int* start,
                              const int* count, int ntiles, double* F0, int compute_f0, double* JT, int ldjt);
+
+/* ---- batched Levenberg-Marquardt: many small curve fits in one launch ----------------- */
+/* nprob independent fits of one kind -- PNOL_OBJ_EXPCURVE (n = 3, ExampleObjectives.hpp:113-154)
+ * or PNOL_OBJ_CUBIC (n = 4, :160-201) -- on m data rows each: one GPU lane runs one problem's
+ * whole LevMarq::findMin (LevenbergMarquardt.cpp:11-167) in the reference's operation order, so
+ * a problem's result is the same bits whatever batch it is solved in, and for Cubic the bits of
+ * the CPU path.  The reference has no batched form: this replaces a host loop of
+ * LevMarq::findMin calls over problems.
+ * host_xdata: xlen == m is one grid shared by every problem, xlen == nprob * m one grid per
+ * problem ([nprob][m] row-major); anything else PNOL_ERR_ARG, as is n != 3 (ExpCurve) / 4 (Cubic)
+ * or nprob <= 0; other kinds PNOL_ERR_UNSUPPORTED.  Uploads x and, for Cubic, pow(x, 3.0)
+ * tabulated on the host (ExampleObjectives.hpp:175). */
+typedef struct pnol_lm_batch pnol_lm_batch;
+int pnol_lm_batch_create(pnol_ctx* ctx, int kind, int n, int m, long long nprob, const double* host_xdata,
+                         size_t xlen, pnol_lm_batch** out);
+int pnol_lm_batch_destroy(pnol_lm_batch* batch);
+/* LevMarq::findMin (LevenbergMarquardt.cpp:11-167) of every problem, queued on the context
+ * stream with no host wait (timer "lm_batch").  yData: nprob * m device doubles, [nprob][m];
+ * params: HOST, 6 doubles in LevMarq::setParams order (lambda0, lambdaFactor, dXGrad, maxIter,
+ * xMinDiff, verbose -- nothing is printed); X: nprob * n, x0 in, optimum out; chi0 / chi: nprob
+ * doubles, chi^2 at x0 and at the optimum; iters: nprob ints, the loop's iter at exit; evals:
+ * nprob long longs, objEval calls the reference would have made; F0 / FOpt (nullable): nprob * m,
+ * F(x0) and F(optimum). */
+int pnol_lm_batch_solve_d(pnol_ctx* ctx, pnol_lm_batch* batch, const double* yData, const double* params, double* X,
+                          double* chi0, double* chi, int* iters, long long* evals, double* F0, double* FOpt);
+/* The same with HOST pointers on the process default context: create, upload, solve, download,
+ * destroy (a loop of LevMarq::setParams + findMin over problems, LevenbergMarquardt.cpp:11-167).
+ * Arguments are checked before any device use; PNOL_ERR_NODEVICE without a gfx950 device. */
+int pnol_run_levmarq_batch(int kind, int n, int m, long long nprob, const double* xdata, size_t xlen,
+                           const double* ydata, const double* params, double* X, double* chi0, double* chi, int* iters,
+                           long long* evals, double* F0, double* FOpt);
 
 /* ---- communicator (replaces MPI_COMM_WORLD on the FD / pool paths) ------------------- */
 /* RCCL over xGMI: one process per GPU.  Exchange the 128-byte id out of band (rank 0 creates). */

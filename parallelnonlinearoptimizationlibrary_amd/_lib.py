@@ -116,6 +116,11 @@ _SIGS = {
     "pnol_lm_trip_d": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _d, _vp, _vp, _vp, _vp]),
     "pnol_lm_trip_normal_d": (_i, [_vp, _i, _i, _d, _vp, _i]),
     "pnol_fd_jacobian_tiles_d": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), _i, _vp, _i, _vp, _i]),
+    "pnol_lm_batch_create": (_i, [_vp, _i, _i, _i, C.c_longlong, _dp, _sz, C.POINTER(_vp)]),
+    "pnol_lm_batch_destroy": (_i, [_vp]),
+    "pnol_lm_batch_solve_d": (_i, [_vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pnol_run_levmarq_batch": (_i, [_i, _i, _i, C.c_longlong, _dp, _sz, _dp, _dp, _dp, _dp, _dp, C.POINTER(_i),
+                                    C.POINTER(C.c_longlong), _dp, _dp]),
     "pnol_comm_unique_id": (_i, [C.c_char_p]),
     "pnol_comm_init_rccl": (_i, [_vp, _i, _i, C.c_char_p]),
     "pnol_comm_init_host": (_i, [_i, _i, ALLGATHER_FN, _vp]),

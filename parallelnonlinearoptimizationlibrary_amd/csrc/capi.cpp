@@ -585,3 +585,124 @@ int pnol_fd_jacobian_tiles_d(pnol_ctx* ctx, pnol_dobj* obj, const double* x, con
 }
 
 }  // extern "C"
+
+// ---- batched Levenberg-Marquardt (lm_batch.hip) -------------------------------------------
+namespace {
+
+// shape checks shared by the create and the host-pointer call; nothing here touches a device
+int lmb_check_shape(int kind, int n, int m, long long nprob, size_t xlen) {
+    if (kind != PNOL_OBJ_EXPCURVE && kind != PNOL_OBJ_CUBIC) return PNOL_ERR_UNSUPPORTED;
+    if (n != (kind == PNOL_OBJ_EXPCURVE ? 3 : 4)) return PNOL_ERR_ARG;
+    if (m <= 0 || nprob <= 0) return PNOL_ERR_ARG;
+    if (xlen != (size_t)m && xlen != (size_t)nprob * (size_t)m) return PNOL_ERR_ARG;
+    return PNOL_OK;
+}
+
+// LevMarq::setParams order; maxIter is a double there and cast to int
+int lmb_check_params(const double* p) {
+    if (!p) return PNOL_ERR_ARG;
+    if (!(p[3] >= 0.0 && p[3] <= 2147483647.0)) return PNOL_ERR_ARG;
+    return PNOL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pnol_lm_batch_create(pnol_ctx* ctx, int kind, int n, int m, long long nprob, const double* host_xdata,
+                         size_t xlen, pnol_lm_batch** out) {
+    if (!out) return PNOL_ERR_ARG;
+    *out = nullptr;
+    PNOL_CHECK(lmb_check_shape(kind, n, m, nprob, xlen));
+    if (!host_xdata) return PNOL_ERR_ARG;
+    PNOL_CHECK(set_device(ctx));
+    auto* b = new pnol_lm_batch();
+    b->kind = kind; b->n = n; b->m = m; b->nprob = (size_t)nprob; b->device = ctx->device;
+    b->per_problem_x = nprob > 1 && xlen == (size_t)nprob * (size_t)m;
+    auto upload = [&](const double* src, double** dst) -> int {
+        if (hipMalloc(dst, sizeof(double) * xlen) != hipSuccess) return PNOL_ERR_NOMEM;
+        PNOL_HIP(hipMemcpy(*dst, src, sizeof(double) * xlen, hipMemcpyHostToDevice));
+        return PNOL_OK;
+    };
+    int st = upload(host_xdata, &b->x);
+    if (st == PNOL_OK && kind == PNOL_OBJ_CUBIC) {
+        // pow(xData[k], 3.0) by the host libm the reference uses, as pnol_dobj_create tabulates it
+        std::vector<double> p3(xlen);
+        for (size_t k = 0; k < xlen; ++k) p3[k] = std::pow(host_xdata[k], 3.0);
+        st = upload(p3.data(), &b->p3);
+    }
+    if (st != PNOL_OK) {
+        pnol_lm_batch_destroy(b);
+        return st;
+    }
+    *out = b;
+    return PNOL_OK;
+}
+
+int pnol_lm_batch_destroy(pnol_lm_batch* b) {
+    if (!b) return PNOL_ERR_ARG;
+    (void)hipSetDevice(b->device);
+    if (b->x) (void)hipFree(b->x);
+    if (b->p3) (void)hipFree(b->p3);
+    (void)hipGetLastError();   // a failed clean-up call must not surface at the next launch check
+    delete b;
+    return PNOL_OK;
+}
+
+int pnol_lm_batch_solve_d(pnol_ctx* ctx, pnol_lm_batch* batch, const double* yData, const double* params, double* X,
+                          double* chi0, double* chi, int* iters, long long* evals, double* F0, double* FOpt) {
+    PNOL_CHECK(set_device(ctx));
+    if (!batch || batch->device != ctx->device) return PNOL_ERR_ARG;
+    PNOL_CHECK(lmb_check_params(params));
+    return launch_lm_batch(ctx, batch, yData, params, X, chi0, chi, iters, evals, F0, FOpt);
+}
+
+int pnol_run_levmarq_batch(int kind, int n, int m, long long nprob, const double* xdata, size_t xlen,
+                           const double* ydata, const double* params, double* X, double* chi0, double* chi, int* iters,
+                           long long* evals, double* F0, double* FOpt) {
+    PNOL_CHECK(lmb_check_shape(kind, n, m, nprob, xlen));
+    PNOL_CHECK(lmb_check_params(params));
+    if (!xdata || !ydata || !X || !chi0 || !chi || !iters || !evals) return PNOL_ERR_ARG;
+    pnol_ctx* ctx = nullptr;
+    PNOL_CHECK(pnol_default_ctx(&ctx));
+    PNOL_CHECK(set_device(ctx));
+    pnol_lm_batch* b = nullptr;
+    PNOL_CHECK(pnol_lm_batch_create(ctx, kind, n, m, nprob, xdata, xlen, &b));
+    const size_t np = (size_t)nprob, nm = np * (size_t)m;
+    // one device block: y | X | chi0 | chi | evals | iters | F0 | FOpt (8-byte items first)
+    const size_t nF = (F0 ? nm : 0) + (FOpt ? nm : 0);
+    const size_t bytes = sizeof(double) * (nm + np * n + 2 * np + nF) + sizeof(long long) * np + sizeof(int) * np;
+    char* dv = nullptr;
+    int st = hipMalloc(&dv, bytes) == hipSuccess ? PNOL_OK : PNOL_ERR_NOMEM;
+    auto hip = [&](hipError_t e) {
+        if (st == PNOL_OK && e != hipSuccess) st = PNOL_ERR_HIP;
+    };
+    if (st == PNOL_OK) {
+        double* dy = (double*)dv;
+        double* dX = dy + nm;
+        double* dc0 = dX + np * n;
+        double* dc = dc0 + np;
+        long long* dev = (long long*)(dc + np);
+        double* dF0 = (double*)(dev + np);
+        double* dFO = dF0 + (F0 ? nm : 0);
+        int* dit = (int*)(dFO + (FOpt ? nm : 0));
+        hip(hipMemcpyAsync(dy, ydata, sizeof(double) * nm, hipMemcpyHostToDevice, ctx->stream));
+        hip(hipMemcpyAsync(dX, X, sizeof(double) * np * n, hipMemcpyHostToDevice, ctx->stream));
+        if (st == PNOL_OK)
+            st = launch_lm_batch(ctx, b, dy, params, dX, dc0, dc, dit, dev, F0 ? dF0 : nullptr, FOpt ? dFO : nullptr);
+        hip(hipMemcpyAsync(X, dX, sizeof(double) * np * n, hipMemcpyDeviceToHost, ctx->stream));
+        hip(hipMemcpyAsync(chi0, dc0, sizeof(double) * np, hipMemcpyDeviceToHost, ctx->stream));
+        hip(hipMemcpyAsync(chi, dc, sizeof(double) * np, hipMemcpyDeviceToHost, ctx->stream));
+        hip(hipMemcpyAsync(evals, dev, sizeof(long long) * np, hipMemcpyDeviceToHost, ctx->stream));
+        hip(hipMemcpyAsync(iters, dit, sizeof(int) * np, hipMemcpyDeviceToHost, ctx->stream));
+        if (F0) hip(hipMemcpyAsync(F0, dF0, sizeof(double) * nm, hipMemcpyDeviceToHost, ctx->stream));
+        if (FOpt) hip(hipMemcpyAsync(FOpt, dFO, sizeof(double) * nm, hipMemcpyDeviceToHost, ctx->stream));
+        if (const int w = stream_wait(ctx->stream))
+            if (st == PNOL_OK) st = w;
+    }
+    if (dv) (void)hipFree(dv);
+    pnol_lm_batch_destroy(b);
+    return st;
+}
+
+}  // extern "C"

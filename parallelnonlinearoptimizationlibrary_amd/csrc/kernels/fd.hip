@@ -21,6 +21,7 @@
 //                        perturbation window
 #include "../pnol_internal.hpp"
 #include "../pnol_comm.hpp"
+#include "multi_residual.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -336,20 +337,7 @@ __global__ void k_scalar_fd_finish(const double* __restrict__ vals, const double
     if (p < cnt) g[p] = (vals[p] - F) / h[i0 + p];
 }
 
-// ---- small residual objectives (ExpCurve, Cubic) ---------------------------------------
-template <int KIND>
-__device__ __forceinline__ double multi_residual(const double* X, int k, const double* xd, const double* yd,
-                                                 const double* p3) {
-    if (KIND == PNOL_OBJ_EXPCURVE) {
-        double func = X[0] * exp(X[1] * xd[k]) + X[2];        // ExampleObjectives.hpp:128
-        return yd[k] - func;
-    } else {
-        double xv = xd[k];                                      // :175, pow(x,3) tabulated
-        double func = X[0] * p3[k] + X[1] * (xv * xv) + X[2] * xv + X[3];
-        return yd[k] - func;
-    }
-}
-
+// ---- small residual objectives (ExpCurve, Cubic): multi_residual.hpp ---------------------
 template <int KIND>
 __global__ void k_multi_eval(const double* __restrict__ x, int n, int m, const double* __restrict__ xd,
                              const double* __restrict__ yd, const double* __restrict__ p3, double* __restrict__ F) {

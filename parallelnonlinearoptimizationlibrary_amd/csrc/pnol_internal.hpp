@@ -152,9 +152,21 @@ struct pnol_dobj {
     }
 };
 
+// A batch of small curve fits (lm_batch.hip): nprob problems of one kind on m data rows each
+struct pnol_lm_batch {
+    int kind = 0;
+    int n = 0;
+    int m = 0;
+    size_t nprob = 0;
+    bool per_problem_x = false;   // x (and p3) hold nprob * m values, else one shared grid of m
+    double* x = nullptr;          // device x grid(s)
+    double* p3 = nullptr;         // Cubic: pow(x, 3.0) tabulated on the host
+    int device = 0;
+};
+
 namespace pnol {
 
-#define PNOL_HIP(expr)                                                                       \
+#define PNOL_HIP(expr)                                                                      \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
         if (e_ != hipSuccess) {                                                              \
@@ -349,6 +361,10 @@ int launch_synthetic_quadratic(pnol_ctx* ctx, unsigned long long seed, int n, do
 int launch_synthetic_linres(pnol_ctx* ctx, unsigned long long seed, int m, int n, double* A, double* xstar,
                             double* y);
 int launch_fill(pnol_ctx* ctx, double* p, size_t count, double value);
+// Every problem's whole LevMarq::findMin in one launch, one lane per problem (lm_batch.hip).
+// params: host, LevMarq::setParams order; X: x0 in, optimum out; F0 / FOpt nullable
+int launch_lm_batch(pnol_ctx* ctx, const pnol_lm_batch* b, const double* y, const double* params, double* X,
+                    double* chi0, double* chi, int* iters, long long* evals, double* F0, double* FOpt);
 
 // ---- LM m-slices: J^T J and J^T F are summed over kLmSlices slices of the m
 // residual rows by a fixed tree (syrk.hip), so LevMarqMPI can split the rows over up to

@@ -300,6 +300,98 @@ class DeviceObjective:
         return F0, JT
 
 
+def _lm_batch_dims(kind, xdata, ydata):
+    """(n, m, nprob, x) of a batch from its arrays: ydata is nprob x m, xdata m or nprob x m values."""
+    if kind not in (L.OBJ_EXPCURVE, L.OBJ_CUBIC):
+        raise L.PnolError(L.PNOL_ERR_UNSUPPORTED, "lm_batch kind")
+    if ydata.ndim != 2:
+        raise ValueError("ydata must be nprob x m")
+    nprob, m = int(ydata.shape[0]), int(ydata.shape[1])
+    x = np.ascontiguousarray(xdata, dtype=np.float64).ravel()
+    return (3 if kind == L.OBJ_EXPCURVE else 4), m, nprob, x
+
+
+class LMBatch:
+    """A pnol_lm_batch: nprob ExpCurve / Cubic fits on m data rows each, solved in one launch
+    (one GPU lane per problem).  xdata: m values (one grid for every problem) or nprob x m."""
+
+    def __init__(self, ctx: Context, kind: int, m: int, nprob: int, xdata):
+        self.ctx, self.kind, self.m, self.nprob = ctx, kind, int(m), int(nprob)
+        self.n = 3 if kind == L.OBJ_EXPCURVE else 4
+        x = np.ascontiguousarray(xdata, dtype=np.float64).ravel()
+        h = C.c_void_p()
+        L.check(L.lib().pnol_lm_batch_create(ctx.h, kind, self.n, self.m, self.nprob, _dptr(x), x.size, C.byref(h)),
+                "pnol_lm_batch_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().pnol_lm_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve(self, ydata, X, params, want_F=False):
+        """LevMarq::findMin of every problem, queued on the context's stream.  ydata (nprob x m)
+        and X (nprob x n: x0 in, optimum out, in place) are float64 torch tensors on the context's
+        device, or array-likes that are uploaded (X is then copied, not updated).  params:
+        LevMarq::setParams order.  Returns (X, chi0, chi, iters, evals[, F0, FOpt]) as torch
+        tensors -- read them after ctx.synchronize() or through torch's stream ordering."""
+        t = self.ctx.torch
+        dev = f"cuda:{self.ctx.device}"
+        y = ydata if t.is_tensor(ydata) else self.ctx.tensor(ydata)
+        Xd = X if t.is_tensor(X) else self.ctx.tensor(X)
+        for a, cnt, what in ((y, self.nprob * self.m, "ydata"), (Xd, self.nprob * self.n, "X")):
+            if a.dtype != t.float64 or not a.is_contiguous() or a.numel() != cnt or not a.is_cuda \
+                    or a.device.index != self.ctx.device:
+                raise ValueError(f"{what}: a contiguous float64 tensor of {cnt} values on {dev} is required")
+        p = np.array(params, dtype=np.float64)
+        if p.size != 6:
+            raise ValueError("params: the 6 values of LevMarq::setParams")
+        chi0, chi = self.ctx.empty(self.nprob), self.ctx.empty(self.nprob)
+        iters = t.empty(self.nprob, dtype=t.int32, device=dev)
+        evals = t.empty(self.nprob, dtype=t.int64, device=dev)
+        F0 = self.ctx.empty(self.nprob, self.m) if want_F else None
+        FO = self.ctx.empty(self.nprob, self.m) if want_F else None
+        L.check(L.lib().pnol_lm_batch_solve_d(self.ctx.h, self.h, _ptr(y), _dptr(p), _ptr(Xd), _ptr(chi0), _ptr(chi),
+                                              _ptr(iters), _ptr(evals), _ptr(F0), _ptr(FO)), "pnol_lm_batch_solve_d")
+        return (Xd, chi0, chi, iters, evals, F0, FO) if want_F else (Xd, chi0, chi, iters, evals)
+
+
+def run_levmarq_batch(ctx, kind, xdata, ydata, x0, params, want_F=False):
+    """Batched LevMarq: nprob independent ExpCurve / Cubic fits in one launch.  ydata: nprob x m;
+    xdata: m values (one shared grid) or nprob x m; x0: nprob x n; params: LevMarq::setParams
+    order.  ctx: a Context (the batch is uploaded and solved on it), or None for the process
+    default context through the host-pointer entry point pnol_run_levmarq_batch.
+    Returns (X, chi0, chi, iters, evals[, F0, FOpt]) as numpy arrays."""
+    y = np.ascontiguousarray(ydata, dtype=np.float64)
+    n, m, nprob, x = _lm_batch_dims(kind, xdata, y)
+    X = np.array(x0, dtype=np.float64).reshape(nprob, n)
+    if ctx is not None:
+        b = LMBatch(ctx, kind, m, nprob, x)
+        try:
+            out = b.solve(y, X, params, want_F)
+            ctx.synchronize()
+            return tuple(a.cpu().numpy() for a in out)
+        finally:
+            b.close()
+    p = np.array(params, dtype=np.float64)
+    chi0, chi = np.zeros(nprob), np.zeros(nprob)
+    iters, evals = np.zeros(nprob, dtype=np.int32), np.zeros(nprob, dtype=np.int64)
+    F0 = np.zeros((nprob, m)) if want_F else None
+    FO = np.zeros((nprob, m)) if want_F else None
+    L.check(L.lib().pnol_run_levmarq_batch(kind, n, m, nprob, _dptr(x), x.size, _dptr(y), _dptr(p), _dptr(X),
+                                           _dptr(chi0), _dptr(chi), iters.ctypes.data_as(C.POINTER(C.c_int)),
+                                           evals.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                           _dptr(F0) if want_F else None, _dptr(FO) if want_F else None),
+            "pnol_run_levmarq_batch")
+    return (X, chi0, chi, iters, evals, F0, FO) if want_F else (X, chi0, chi, iters, evals)
+
+
 def lm_rank_rows(m, nranks, rank):
     """Residual rows [r0, r1) held by `rank` of `nranks` (its m-slices; rows mode's F0 rows)."""
     r0, r1 = C.c_int(), C.c_int()
