@@ -5,14 +5,12 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "../pnol_env.hpp"
 #include "PNOL_Objective.hpp"
 
 namespace pnol {
 
-static bool shard_enabled() {
-    const char* e = std::getenv("PNOL_BFGS_SHARD");
-    return !e || std::atoi(e) != 0;
-}
+static bool shard_enabled() { return env_default_on("PNOL_BFGS_SHARD"); }
 
 void DenseInverseHessian::init(int mode, bool shard) {
     exact_ = mode == 1 || (mode == 0 && n_ <= PNOL_SEQ_MAX);

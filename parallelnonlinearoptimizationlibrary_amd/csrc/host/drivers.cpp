@@ -20,6 +20,7 @@
 #include "LevenbergMarquardtMPI.hpp"
 #include "device_util.hpp"
 #include "scalar_host.hpp"
+#include "../pnol_env.hpp"
 #include "../pnol_internal.hpp"
 
 using namespace pnol;
@@ -74,8 +75,7 @@ class DriverScalar : public Objective {
         return ScalarTerms{d_->kind, n, d_->power, p0_.data(), p1_.data()};
     }
     static bool device_points() {
-        const char* e = std::getenv("PNOL_DEVICE_POINTS");   // read per call (tests flip it)
-        return e && std::atoi(e) != 0;
+        return env_atoi("PNOL_DEVICE_POINTS", 0) != 0;   // read per call (tests flip it)
     }
     pnol_dobj* d_;
     bool host_only_;

@@ -12,6 +12,7 @@
 #include <utility>
 
 #include "../pnol_comm.hpp"
+#include "../pnol_env.hpp"
 #include "../pnol_internal.hpp"
 #include "LevenbergMarquardt.hpp"
 #include "LevenbergMarquardtMPI.hpp"
@@ -218,14 +219,11 @@ class LMAsync {
         // steps: 5 of 5 alternating same-box pairs slower than the two calls, 317-321 vs
         // 324-328.5 LM iters/s, profiles/r05_trip_ab.txt; PNOL_LM_REDUCE=tasks keeps that form.)
         {
-            const char* e = std::getenv("PNOL_LM_TRIP");
-            trip_fused_ = !e || std::atoi(e) != 0;
-            const char* z = std::getenv("PNOL_LM_ZEROCOPY");
-            zero_copy_ = trip_fused_ && !sliced && (!z || std::atoi(z) != 0);
+            trip_fused_ = env_default_on("PNOL_LM_TRIP");
+            zero_copy_ = trip_fused_ && !sliced && env_default_on("PNOL_LM_ZEROCOPY");
             // the next trip's Jacobian queued behind a gate while the host decides (PNOL_LM_GATE=0:
             // queued after the decision, as the rest of the trip)
-            const char* g = std::getenv("PNOL_LM_GATE");
-            gate_ok_ = zero_copy_ && (!g || std::atoi(g) != 0);
+            gate_ok_ = zero_copy_ && env_default_on("PNOL_LM_GATE");
             // how long a gate waits for the decision (ticks of 100 MHz; default 1 s; a test sets 0
             // to exercise the repeat of a trip whose gate gave up)
             const char* c = std::getenv("PNOL_LM_GATE_CAP");
@@ -441,15 +439,13 @@ class LMAsync {
 };
 
 bool lm_async_enabled() {
-    const char* e = std::getenv("PNOL_LM_ASYNC");   // read per solve (tests compare both loops)
-    return !e || std::atoi(e) != 0;
+    return env_default_on("PNOL_LM_ASYNC");   // read per solve (tests compare both loops)
 }
 
 // The sliced LevMarqMPI form: linear-residual device objectives, up to PNOL_LM_SLICES ranks
 // (PNOL_LM_SLICED=0 keeps the column-sharded general loop)
 bool lm_sliced_ok(pnol_dobj* d) {
-    const char* e = std::getenv("PNOL_LM_SLICED");
-    if (e && std::atoi(e) == 0) return false;
+    if (!env_default_on("PNOL_LM_SLICED")) return false;
     int kind = 0, n = 0, m = 0;
     return pnol_dobj_info(d, &kind, &n, &m) == PNOL_OK && kind == PNOL_OBJ_LINRES && comm_size() <= PNOL_LM_SLICES;
 }

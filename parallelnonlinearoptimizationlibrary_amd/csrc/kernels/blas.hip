@@ -14,6 +14,7 @@
 // All device code is compiled with -ffp-contract=off: every fma here is explicit.
 #include "../pnol_internal.hpp"
 #include "../pnol_comm.hpp"
+#include "../pnol_env.hpp"
 
 #include <cstdlib>
 
@@ -595,17 +596,11 @@ int launch_gemv_neg(pnol_ctx* ctx, const double* A, int lda, int rows, int cols,
     // rows per wave: enough waves to cover the chip (>= ~2 per SIMD) with long streams each;
     // more rows per wave amortise the x reads (every wave streams all of x from L2).
     // PNOL_GEMV_ROWS=1|2|4 overrides the choice (tuning sweeps, tools/sweep_hg.py).
-    static const int forced = [] {
-        const char* e = std::getenv("PNOL_GEMV_ROWS");
-        return e ? std::atoi(e) : 0;
-    }();
+    static const int forced = env_atoi("PNOL_GEMV_ROWS", 0);
     // PNOL_GEMV_MODE (tuning): 0 wave per R rows, 1 workgroup-cooperative rows, 2 (default)
     // = 1 with non-temporal loads: 6.66 TB/s at n = 8192 vs 4.0 for the best cached variant
     // (profiles/r01_sweep_hg.log)
-    static const int mode = [] {
-        const char* e = std::getenv("PNOL_GEMV_MODE");
-        return e ? std::atoi(e) : 2;
-    }();
+    static const int mode = env_atoi("PNOL_GEMV_MODE", 2);
     if (mode == 1 || mode == 2) {
         const int Rw = forced == 1 || forced == 2 || forced == 4 ? forced : 2;
         const int blocks = (rows + Rw - 1) / Rw;
@@ -636,8 +631,7 @@ int launch_gemv_neg_slices(pnol_ctx* ctx, const double* A, int lda, long sstride
     if (!A || !x || !y || rows <= 0 || nsl <= 0 || (mS & 1)) return PNOL_ERR_ARG;
     // rows per workgroup (PNOL_JTR_ROWS = 1, 2 or 4; tuning -- each row's sum is the same for all)
     static const int R = [] {
-        const char* e = std::getenv("PNOL_JTR_ROWS");
-        const int v = e ? std::atoi(e) : 2;
+        const int v = env_atoi("PNOL_JTR_ROWS", 2);
         return (v == 1 || v == 4) ? v : 2;
     }();
     // 16-byte row loads when every row start is 16-byte aligned; the same sums otherwise
@@ -683,8 +677,7 @@ int launch_bfgs_update_exact(pnol_ctx* ctx, double* D, int ldd, const double* y,
 // rows [rb, re) only.
 int bfgs_pass_rows(int n) {
     static const int forced = [] {
-        const char* e = std::getenv("PNOL_PASS_ROWS");
-        const int v = e ? std::atoi(e) : 0;
+        const int v = env_atoi("PNOL_PASS_ROWS", 0);
         return (v == 32 || v == 64 || v == 128 || v == 256) ? v : 0;
     }();
     if (forced) return forced;

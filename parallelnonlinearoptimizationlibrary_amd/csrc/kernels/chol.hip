@@ -23,6 +23,7 @@
 #include "../pnol_internal.hpp"
 #include "../pnol_comm.hpp"
 #include "../chol_tasks.hpp"
+#include "../pnol_env.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -2076,12 +2077,6 @@ __global__ void k_flag_info(int* info, int v) { *info = v; }
 // afterwards when a pivot failed or a chain timed out.
 // PNOL_CHOL_PERSIST = 0 / 1 (read per call: the tests switch it) selects the per-step launches
 // (method 4) or the persistent form; `variant` 4 / 5 forces one.
-// a default-on switch of the environment: unset is on, otherwise its integer value != 0
-static bool env_default_on(const char* name) {
-    const char* e = std::getenv(name);
-    return !e || std::atoi(e) != 0;
-}
-
 static bool chol_persistent(int variant) {
     if (variant == 4) return false;
     if (variant == 5) return true;
@@ -2152,8 +2147,6 @@ static int chol_persist_launch(pnol_ctx* ctx, hipStream_t st, const CholWs& w, i
     // tuning knob (read per call): PNOL_CHOL5_WORKERS = worker workgroups; one per CU
     // (the look-ahead areas already hold the static LDS to one workgroup per CU).
     // PNOL_CHOL_LOOKAHEAD = 0 turns the diagonal chain's look-ahead off (read per call).
-    const char* ew = std::getenv("PNOL_CHOL5_WORKERS");
-    const char* el = std::getenv("PNOL_CHOL_LOOKAHEAD");
     // > 0: the look-ahead gives up once wave 0 has finished that many columns of the tile
     // (0 off; above 64: the factor waits for the next tiles).  The next tiles wait on a panel and
     // an update task (~6 us each after W_{d-1}), so a look-ahead that starts late runs past the
@@ -2166,7 +2159,7 @@ static int chol_persist_launch(pnol_ctx* ctx, hipStream_t st, const CholWs& w, i
     // (EarlyNext mode 3): their step's prepare skips the loads, ~4.5k of its ~10.5k cycles, and
     // the solve goes 0.559-0.561 -> 0.553-0.556 ms; with it every cutoff from 1 to 48 measures
     // the same (56: 0.562-0.566), profiles/r05_lookahead_sweep.txt.
-    const int lookahead = el ? std::max(0, std::atoi(el)) : 48;
+    const int lookahead = std::max(0, env_atoi("PNOL_CHOL_LOOKAHEAD", 48));
     {
         // order 1 (each step's critical tasks a step early) lets a critical set's worth of workers
         // wait on tasks nobody has claimed yet, so it needs more workers than that resident
@@ -2174,11 +2167,10 @@ static int chol_persist_launch(pnol_ctx* ctx, hipStream_t st, const CholWs& w, i
         // several processes may hold fewer (a 4-process run at cfg 3 stalled one trip until the
         // spin cap, profiles/r06_chol_contention_4p_cfg3.json): ranks sharing the GPU over the
         // host backend, and a context that has seen a timed-out wait, claim in step order.
-        const char* eo = std::getenv("PNOL_CHOL_ORDER");
-        rp.order = eo ? (std::atoi(eo) != 0 ? 1 : 0) : ((ctx->chol_order0 || comm_shares_device()) ? 0 : 1);
+        rp.order = env_atoi("PNOL_CHOL_ORDER", (ctx->chol_order0 || comm_shares_device()) ? 0 : 1) != 0 ? 1 : 0;
     }
     const int slots = std::max(ctx->num_cu, 1) - 1;
-    const int want = ew ? std::atoi(ew) : slots;
+    const int want = env_atoi("PNOL_CHOL5_WORKERS", slots);
     const int nred = (red.part || red.packed) ? chol_reduce_task_count(T) : 0;
     const int workers = std::max(1, std::min(ntasks + nred, want));
     hipLaunchKernelGGL(k_chol_persist, dim3(1 + workers), dim3(256), 0, st, w.P, w.Lm, w.ldp, T, w.W, w.bv, w.zv, w.pf,
@@ -2205,12 +2197,10 @@ static int chol_bwd_launch(pnol_ctx* ctx, hipStream_t st, const CholWs& w, int n
     // callers' LU paths run on an SPD system; kCholTimeout (-7) reports a timed-out wait on the LM
     // trip's solves only (`trip`: the reducing form, pnol_solve_step_d), so the caller's relaunch
     // -- pnol_solve_d, which is not forced -- runs
-    if (const char* e = std::getenv("PNOL_CHOL_FORCE_FALLBACK")) {
-        const int v = std::atoi(e);
-        if (v > 0 || (v == kCholTimeout && trip)) {
-            hipLaunchKernelGGL(k_flag_info, dim3(1), dim3(1), 0, st, dinfo, v);
-            return launch_check();
-        }
+    const int v = env_atoi("PNOL_CHOL_FORCE_FALLBACK", 0);
+    if (v > 0 || (v == kCholTimeout && trip)) {
+        hipLaunchKernelGGL(k_flag_info, dim3(1), dim3(1), 0, st, dinfo, v);
+        return launch_check();
     }
     return PNOL_OK;
 }

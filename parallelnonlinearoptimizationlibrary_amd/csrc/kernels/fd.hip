@@ -21,6 +21,7 @@
 //                        perturbation window
 #include "../pnol_internal.hpp"
 #include "../pnol_comm.hpp"
+#include "../pnol_env.hpp"
 #include "multi_residual.hpp"
 
 #include <algorithm>
@@ -873,10 +874,7 @@ int launch_fd_gradient(pnol_ctx* ctx, pnol_dobj* o, const double* x, const doubl
     PNOL_CHECK(ws_get(ctx, "fd_terms", sizeof(double) * (size_t)o->n, &terms));
     double *V = (double*)vals, *T = (double*)terms;
     // PNOL_FD_SCALAR=0: the point-per-thread form (every term recomputed; tuning / cross-check)
-    static const bool chain = [] {
-        const char* e = std::getenv("PNOL_FD_SCALAR");
-        return !e || std::atoi(e) != 0;
-    }();
+    static const bool chain = env_default_on("PNOL_FD_SCALAR");
     if (xdev && !chain) {   // the point-per-thread form reads x throughout: bring it to the device
         PNOL_HIP(hipMemcpyAsync(xdev, x, sizeof(double) * (size_t)o->n, hipMemcpyHostToDevice, ctx->stream));
         x = xdev;
@@ -1004,10 +1002,7 @@ int launch_fd_jacobian_tiles(pnol_ctx* ctx, pnol_dobj* o, const double* x, const
     const int per_launch = after_tile ? 1 : kFdMaxTiles;
     // 16 points per wave when a launch would hold <= 2 waves per SIMD at 32 (k_linres_fdP);
     // PNOL_FD_PW = 16 / 32 forces either (A/B measurement)
-    static const int force_pw = [] {
-        const char* e = std::getenv("PNOL_FD_PW");
-        return e ? std::atoi(e) : 0;
-    }();
+    static const int force_pw = env_atoi("PNOL_FD_PW", 0);
     if (gate.hw) {
         hipLaunchKernelGGL(k_trip_gate, dim3(1), dim3(64), 0, ctx->stream, gate.hw, gate.seq, gate.sel, gate.res,
                            gate.cap);
@@ -1113,17 +1108,12 @@ int launch_synthetic_linres(pnol_ctx* ctx, unsigned long long seed, int m, int n
 }
 
 int lm_phased_env() {
-    const char* e = std::getenv("PNOL_LM_PHASED");
-    if (e && std::atoi(e) == 0) return 0;
-    const char* s = std::getenv("PNOL_LM_SUBPHASES");   // column groups of each rank's last tile
-    const int v = s ? std::atoi(s) : kLmSubphases;
+    if (!env_default_on("PNOL_LM_PHASED")) return 0;
+    const int v = env_atoi("PNOL_LM_SUBPHASES", kLmSubphases);   // column groups of each rank's last tile
     return std::min(8, std::max(1, v));
 }
 
-int lm_fd_mode_env() {
-    const char* e = std::getenv("PNOL_LM_FD");
-    return (e && std::strcmp(e, "rows") == 0) ? 1 : 0;
-}
+int lm_fd_mode_env() { return env_equals("PNOL_LM_FD", "rows") ? 1 : 0; }
 
 bool lm_rows_mode(pnol_ctx* ctx) {
     if (ctx->lm_fd_mode < 0) ctx->lm_fd_mode = lm_fd_mode_env();

@@ -22,6 +22,7 @@
 // wave-uniform address.  Small problems are staged once and stay resident for the whole solve
 // (kLmbResident); larger ones are re-staged in kLmbRows-row chunks, twice per trip, from L2.
 #include "../pnol_internal.hpp"
+#include "../pnol_env.hpp"
 #include "multi_residual.hpp"
 
 #include <cstdlib>
@@ -275,15 +276,8 @@ __global__ __launch_bounds__(kLmbLanes) void k_lm_batch(const double* __restrict
 }
 
 // PNOL_LMB_ROWS (tuning): a positive value fixes the rows per staged chunk (>= m: all resident)
-bool lmb_rows_set() {
-    const char* e = std::getenv("PNOL_LMB_ROWS");
-    return e && std::atoi(e) > 0;
-}
-int lmb_rows_env() {
-    const char* e = std::getenv("PNOL_LMB_ROWS");
-    const int v = e ? std::atoi(e) : 0;
-    return v > 0 ? v : kLmbRows;
-}
+bool lmb_rows_set() { return env_atoi("PNOL_LMB_ROWS", 0) > 0; }
+int lmb_rows_env() { return lmb_rows_set() ? env_atoi("PNOL_LMB_ROWS", 0) : kLmbRows; }
 
 template <int KIND, bool PERX>
 int lmb_launch(pnol_ctx* ctx, const pnol_lm_batch* b, const double* y, const double* prm, double* X, double* chi0,

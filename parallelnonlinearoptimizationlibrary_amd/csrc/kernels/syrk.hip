@@ -15,10 +15,9 @@
 //   k_jtj_seq       n <= PNOL_SEQ_MAX: the reference's summation order, bitwise.
 #include "../pnol_internal.hpp"
 #include "../pnol_comm.hpp"
+#include "../pnol_env.hpp"
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -27,8 +26,7 @@ namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-constexpr int kTile = 128;
-constexpr int kTK = 16;
+// kTile = 128 and kTK = 16 are lm_normal_plan.hpp's
 constexpr int kPad = 18;   // LDS row stride in doubles
 
 // Diagonal tiles (ti == tj) of the 8-wave 128-row kernel compute only their 36 lower 16 x 16
@@ -665,68 +663,69 @@ __global__ void k_jtj_seq(const double* __restrict__ JT, long ldjt, int m, int n
 
 }  // namespace
 
-// K split: kLmSlices m-slices of mS rows (a multiple of 64, so an FD row panel never straddles
-// two), each cut into `sub` chunks.  sub depends on (m, n) only -- never on the number of
-// ranks -- so every A element is summed the same way on any P.  Default: enough workgroups to
-// fill the chip (>= 2048 = 256 CUs x 2 resident x 4 rounds), chunks >= 256 columns.  At
-// m = 16384, n = 2048 (136 tiles) sub = 2: 2176 workgroups of K = 1024 (measured: SYRK 1.33 ms
-// + reduce 0.09 ms, vs 1.42 + 0.05 ms at sub = 1).  PNOL_SYRK_SUB overrides.
-struct SliceCfg {
-    int mS, sub, kfirst, kchunk;
-};
-
-// k_syrk_reduce with the sub-chunk count as a template constant where it is 1, 2 or 4
-// (grid.x = 128 / 32 strips per tile at SR = 32; SR = 16 launches twice the workgroups)
-template <int SR, typename... Args>
-static void launch_reduce_sr(dim3 grid, dim3 block, size_t shm, hipStream_t st, const double* part, int ntiles,
-                             int sub, Args... args) {
-    grid.x = grid.x * 32 / SR;
-    if (sub == 1)
-        hipLaunchKernelGGL((k_syrk_reduce<1, SR>), grid, block, shm, st, part, ntiles, sub, args...);
-    else if (sub == 2)
-        hipLaunchKernelGGL((k_syrk_reduce<2, SR>), grid, block, shm, st, part, ntiles, sub, args...);
-    else if (sub == 4)
-        hipLaunchKernelGGL((k_syrk_reduce<4, SR>), grid, block, shm, st, part, ntiles, sub, args...);
-    else
-        hipLaunchKernelGGL((k_syrk_reduce<0, SR>), grid, block, shm, st, part, ntiles, sub, args...);
+// The launch plan (lm_normal_plan.hpp) of an (m, n) problem on rank `rank` of P; the K-split
+// switches PNOL_SYRK_SUB / PNOL_SYRK_FIRST are read once per process.
+static LmNormalPlan plan_for(int m, int n, int P = 1, int rank = 0) {
+    static const int forced = env_atoi("PNOL_SYRK_SUB", 0), first_pct = env_atoi("PNOL_SYRK_FIRST", 75);
+    return lm_normal_plan(m, n, P, rank, forced, first_pct);
 }
 
-// 16-row strips: 70 us vs 77 us for 32-row strips at n = 2048, sub = 2
-template <typename... Args>
-static void launch_reduce(dim3 grid, dim3 block, size_t shm, hipStream_t st, const double* part, int ntiles, int sub,
-                          Args... args) {
-    launch_reduce_sr<16>(grid, block, shm, st, part, ntiles, sub, args...);
+// "syrk_part" for `elems` doubles.  The one place that hands it out, and so the one that drops
+// what the last trip left in it (lm_trip_tiles); keep: for the reader of the trip's partials.
+static int part_ws(pnol_ctx* ctx, size_t elems, double** part, bool keep = false) {
+    if (!keep) ctx->lm_trip_tiles.kind = 0;
+    return ws_get(ctx, "syrk_part", sizeof(double) * elems, (void**)part);
+}
+// a trip without A left its split-K partials (kind 1) or its allgathered tiles (kind 2)
+static void trip_tiles_left(pnol_ctx* ctx, const LmNormalPlan& pl, int kind) {
+    ctx->lm_trip_tiles = {kind, pl.m, pl.n, pl.P};
+}
+static int jtr_ws(pnol_ctx* ctx, const LmNormalPlan& pl, double** jp) {
+    return ws_get(ctx, "jtr_part", sizeof(double) * pl.jtr_elems(), (void**)jp);
+}
+static int packed_ws(pnol_ctx* ctx, const LmNormalPlan& pl, double** packed) {
+    return ws_get(ctx, "lm_packed", sizeof(double) * pl.packed_elems(), (void**)packed);
 }
 
-static SliceCfg slice_cfg(int m, int ntiles) {
-    static const int forced = [] {
-        const char* e = std::getenv("PNOL_SYRK_SUB");
-        return e ? std::atoi(e) : 0;
-    }();
-    SliceCfg c;
-    c.mS = lm_slice_rows(m);
-    const int cap = std::max(1, c.mS / 256);
-    if (forced > 0) {
-        c.sub = std::min(forced, std::max(1, c.mS / kTK));
-    } else {
-        const int want = (2048 + ntiles * kS - 1) / (ntiles * kS);
-        c.sub = std::max(1, std::min(want, cap));
+// The reduce of tiles [tile0, tile0 + ntl) from their partials into A (or the Cholesky's padded P,
+// then bv its b); jp / rhs (both or neither): -J^T F's slice tree folded in as one more row of
+// blocks.  k_syrk_reduce with the sub-chunk count as a template constant where it is 1, 2 or 4,
+// in 16-row strips: 70 us vs 77 us for 32-row strips at n = 2048, sub = 2.
+static void launch_reduce(hipStream_t st, const LmNormalPlan& pl, const double* part, int tile0, int ntl, double lambda,
+                          double* A, long lda, double* jtj_diag, const double* jp = nullptr, double* rhs = nullptr,
+                          double* bv = nullptr) {
+    const int sub = pl.sc.sub;
+    const auto k = sub == 1 ? k_syrk_reduce<1, 16> : sub == 2 ? k_syrk_reduce<2, 16> : sub == 4 ? k_syrk_reduce<4, 16>
+                                                                                               : k_syrk_reduce<0, 16>;
+    hipLaunchKernelGGL(k, dim3(kTile / 16, ntl + (jp ? 1 : 0)), dim3(256), 0, st, part, ntl, sub, pl.n, lambda, A, lda,
+                       jtj_diag, tile0, jp, rhs, bv);
+}
+
+// k_syrk_red's instantiation: the sub-chunk count at compile time where it is 2 (the diagonal
+// tiles last only there), write-through partials (sc1) or the release fence
+using SyrkRedKernel = decltype(&k_syrk_red<0, false, false>);
+static SyrkRedKernel syrk_red_kernel(int sub, bool sc1, bool dlast) {
+    if (sub != 2) return sc1 ? k_syrk_red<0, true, false> : k_syrk_red<0, false, false>;
+    if (dlast) return sc1 ? k_syrk_red<2, true, true> : k_syrk_red<2, false, true>;
+    return sc1 ? k_syrk_red<2, true, false> : k_syrk_red<2, false, false>;
+}
+
+static int launch_unpack(pnol_ctx* ctx, const LmNormalPlan& pl, const double* packed, long slot, double lambda,
+                         double* A, long lda, double* jtj_diag) {
+    hipLaunchKernelGGL(k_syrk_unpack, dim3(8, pl.ntiles), dim3(256), 0, ctx->stream, packed, pl.ntiles, pl.n, lambda,
+                       slot, pl.tpr, A, lda, jtj_diag);
+    return launch_check();
+}
+
+// the plan's node list as k_tree_combine's table: node c read at ptr_of(c)
+template <typename F>
+static TreeNodes tree_table(const LmNormalPlan& pl, F ptr_of) {
+    TreeNodes tn{};
+    for (int c = 0; c < pl.NC; ++c) {
+        tn.w[pl.node_lo[c]] = pl.node_w[c];
+        tn.p[pl.node_lo[c]] = ptr_of(c);
     }
-    c.kchunk = ((c.mS + c.sub - 1) / c.sub + kTK - 1) / kTK * kTK;
-    c.kfirst = c.kchunk;
-    // Chunk 0 takes 75% of the slice (PNOL_SYRK_FIRST = percent; the rest split evenly over
-    // chunks 1..sub-1) and is dispatched first (k_syrk_tile's order): 1088 long workgroups, then
-    // 1088 short ones that fill the tail of the last dispatch round.  Measured at m = 16384,
-    // n = 2048: 1.265 ms vs 1.326 ms for two equal chunks (tools/syrk_sweep.py).
-    static const int first_pct = [] {
-        const char* e = std::getenv("PNOL_SYRK_FIRST");
-        return e ? std::atoi(e) : 75;
-    }();
-    if (c.sub >= 2 && first_pct > 0 && first_pct < 100) {
-        c.kfirst = std::max(kTK, (int)((long)c.mS * first_pct / 100) / kTK * kTK);
-        c.kchunk = ((c.mS - c.kfirst + c.sub - 2) / (c.sub - 1) + kTK - 1) / kTK * kTK;
-    }
-    return c;
+    return tn;
 }
 
 // 8 waves per 128 x 128 tile (1.35 ms vs 1.40 ms with 4 at m = 16384, n = 2048).  (A split-K
@@ -740,41 +739,47 @@ static SliceCfg slice_cfg(int m, int ntiles) {
 // m-slice) gets 1056 workgroups instead of 272; on the row-major J^T (128 KB row stride) the
 // 64-row tiles are slower (1.35 vs 1.28 ms), so that layout keeps 128.  PNOL_SYRK_T64 = 0 / 1
 // forces either (read per call: tests switch it).
-static bool syrk_t64(bool sliced) {
-    const char* e = std::getenv("PNOL_SYRK_T64");
-    return e ? std::atoi(e) != 0 : sliced;
-}
+static bool syrk_t64(bool sliced) { return env_atoi("PNOL_SYRK_T64", sliced) != 0; }
 
 // Partial tiles [tile0, tile0 + ntl) x slices [slice0, slice0 + nsl) x sub-chunks of
-// X (nr rows, K columns; slice s at X + s * sstride, row stride ldx) into
+// X (pl.n rows, pl.m columns; slice s at X + s * sstride, row stride ldx) into
 // part[((t - tile0) * nsl * sub + (s - slice0) * sub + u) * 128^2].
 static void syrk_partials(pnol_ctx* ctx, hipStream_t stream, bool rows_variant, const double* X, long ldx,
-                          long sstride, int nr, int K, const SliceCfg& sc, int slice0, int nsl, int tile0, int ntl,
-                          double* part, bool t64 = false) {
-    const int split = nsl * sc.sub;
-    const dim3 grid(ntl * split);
+                          long sstride, const LmNormalPlan& pl, int slice0, int nsl, int tile0, int ntl, double* part,
+                          bool t64 = false) {
+    const SliceCfg& sc = pl.sc;
+    const int nr = pl.n, K = pl.m, split = nsl * sc.sub;
     LaunchTimer tm(ctx, rows_variant ? "syrk_rows" : "syrk");
-    if (t64) {   // all tiles (tile0 = 0): ntl counts the 64 x 64 lower tiles
-        const int nt64 = (nr + 63) / 64;
-        hipExtLaunchKernelGGL((k_syrk_tile<4, 64>), dim3(nt64 * (nt64 + 1) / 2 * split), dim3(256), 0, stream,
-                              tm.start(), tm.stop(), 0, X, ldx, nr, K, split, sc.kfirst, sc.kchunk, sc.sub, slice0,
-                              sc.mS, sstride, part, 0);
-    } else if (rows_variant) {
-        hipExtLaunchKernelGGL((k_syrk_tile<2, kTile, 8>), grid, dim3(512), 0, stream, tm.start(), tm.stop(), 0, X, ldx,
-                              nr, K, split, sc.kfirst, sc.kchunk, sc.sub, slice0, sc.mS, sstride, part, tile0);
-    } else {
-        // plain partial stores: the reduce (or the reducing Cholesky) that reads them next finds
-        // part of them in the caches -- solve 0.71 vs 0.73 ms, SYRK unchanged, in alternating
-        // same-box runs (non-temporal stores for J itself in the FD kernel measured slower; so did
-        // non-temporal partials again in round 5: SYRK +10-30 us)
-        hipExtLaunchKernelGGL((k_syrk_tile<0, kTile, 8, false>), grid, dim3(512), 0, stream, tm.start(), tm.stop(), 0,
-                              X, ldx, nr, K, split, sc.kfirst, sc.kchunk, sc.sub, slice0, sc.mS, sstride, part, tile0);
-    }
+    // t64: all tiles (tile0 = 0, ntl = ntiles) as the 64 x 64 lower tiles instead.  The whole-matrix
+    // 128-row form with plain partial stores: the reduce (or the reducing Cholesky) that reads them
+    // next finds part of them in the caches -- solve 0.71 vs 0.73 ms, SYRK unchanged, in alternating
+    // same-box runs (non-temporal stores for J itself in the FD kernel measured slower; so did
+    // non-temporal partials again in round 5: SYRK +10-30 us)
+    const auto k = t64 ? k_syrk_tile<4, 64> : rows_variant ? k_syrk_tile<2, 128, 8> : k_syrk_tile<0, 128, 8, false>;
+    hipExtLaunchKernelGGL(k, dim3((t64 ? pl.ntiles64 : ntl) * split), dim3(t64 ? 256 : 512), 0, stream, tm.start(),
+                          tm.stop(), 0, X, ldx, nr, K, split, sc.kfirst, sc.kchunk, sc.sub, slice0, sc.mS, sstride, part,
+                          t64 ? 0 : tile0);
 }
 
-static int jtr_gemv(pnol_ctx* ctx, const double* JT, int ldjt, long sstride, int m, int n, int mS, int s0, int nsl,
-                    const double* F, hipStream_t stream = nullptr);
-static int jtr_tree(pnol_ctx* ctx, int n, int s0, int nsl, double* out);
+// -J^T F on the plan's m-slices [s0, s1): jp[(s - s0) * n + j] = -sum_{k in slice s} JT_jk F_k
+// (JT slice s at JT + s * sstride, row stride ldjt), then the slice nodes of that range into
+// out[c * n + j] (one node = -J^T F itself when the range is all kLmSlices slices).
+static int jtr_gemv(pnol_ctx* ctx, const LmNormalPlan& pl, const double* JT, int ldjt, long sstride, const double* F,
+                    double** jp_out = nullptr) {
+    if (!F) return PNOL_ERR_ARG;
+    double* jp = nullptr;
+    PNOL_CHECK(jtr_ws(ctx, pl, &jp));
+    if (jp_out) *jp_out = jp;
+    return launch_gemv_neg_slices(ctx, JT, ldjt, sstride, pl.n, pl.m, pl.sc.mS, pl.s0, pl.nsl(), F, jp);
+}
+
+static int jtr_tree(pnol_ctx* ctx, const LmNormalPlan& pl, double* out) {
+    double* jp = nullptr;
+    PNOL_CHECK(jtr_ws(ctx, pl, &jp));
+    hipLaunchKernelGGL(k_tree_nodes, dim3((pl.n + 255) / 256, 1), dim3(256), 0, ctx->stream, (const double*)jp, 0L,
+                       (long)pl.n, 1, pl.s0, pl.s1, pl.n, out, (long)pl.n, 0L);
+    return launch_check();
+}
 
 int launch_jtj(pnol_ctx* ctx, const double* JT, int ldjt, int m, int n, double lambda, double* A, int lda,
                double* jtj_diag, const double* F, double* rhs) {
@@ -785,49 +790,32 @@ int launch_jtj(pnol_ctx* ctx, const double* JT, int ldjt, int m, int n, double l
         PNOL_CHECK(launch_check());
         return rhs ? launch_jtr(ctx, JT, ldjt, m, n, F, rhs) : PNOL_OK;
     }
-    const int nt = (n + kTile - 1) / kTile;
-    const int ntiles = nt * (nt + 1) / 2;
-    const SliceCfg sc = slice_cfg(m, ntiles);
-    void* part = nullptr;
-    ctx->lm_trip_tiles.kind = 0;   // the trip's tiles are overwritten below
-    PNOL_CHECK(ws_get(ctx, "syrk_part", sizeof(double) * (size_t)ntiles * kS * sc.sub * kTile * kTile, &part));
-    syrk_partials(ctx, ctx->stream, false, JT, ldjt, sc.mS, n, m, sc, 0, kS, 0, ntiles, (double*)part,
-                  syrk_t64(false));
+    const LmNormalPlan pl = plan_for(m, n);
+    double *part = nullptr, *jp = nullptr;
+    PNOL_CHECK(part_ws(ctx, pl.part_elems(), &part));
+    syrk_partials(ctx, ctx->stream, false, JT, ldjt, pl.sc.mS, pl, 0, kS, 0, pl.ntiles, part, syrk_t64(false));
     PNOL_CHECK(launch_check());
-    if (rhs) PNOL_CHECK(jtr_gemv(ctx, JT, ldjt, sc.mS, m, n, sc.mS, 0, kS, F));
+    if (rhs) PNOL_CHECK(jtr_gemv(ctx, pl, JT, ldjt, pl.sc.mS, F, &jp));
     // -J^T F's slice tree rides in the reduce launch (an extra row of blocks).  (The GEMV on a
     // second stream released by the SYRK's last-dispatched workgroup -- hipStreamWaitValue32 on a
     // tail word -- measured slower, 305-311 vs 314-317 LM iters/s: its HBM stream slowed the
     // SYRK's last workgroups more than it hid; removed.)
-    const bool fold = rhs != nullptr;
-    void* jp = nullptr;
-    if (fold) PNOL_CHECK(ws_get(ctx, "jtr_part", sizeof(double) * (size_t)kS * n, &jp));
-    {
-        ScopedTimer tm(ctx, "syrk_reduce");
-        launch_reduce(dim3(kTile / 32, ntiles + (fold ? 1 : 0)), dim3(256), 0, ctx->stream, (const double*)part,
-                      ntiles, sc.sub, n, lambda, A, (long)lda, jtj_diag, 0, (const double*)jp,
-                      fold ? rhs : (double*)nullptr);
-        PNOL_CHECK(launch_check());
-    }
-    return PNOL_OK;
+    ScopedTimer tm(ctx, "syrk_reduce");
+    launch_reduce(ctx->stream, pl, part, 0, pl.ntiles, lambda, A, lda, jtj_diag, jp, rhs);
+    return launch_check();
 }
 
 int launch_jtj_rows(pnol_ctx* ctx, hipStream_t stream, const double* JT, int ldjt, int m, int n, double lambda,
                     double* A, int lda, double* jtj_diag, int row_begin, int row_end) {
-    const int nt = (n + kTile - 1) / kTile;
-    const int ntiles = nt * (nt + 1) / 2;
-    if (row_begin < 0 || row_end > nt || row_begin >= row_end) return PNOL_ERR_ARG;
-    const SliceCfg sc = slice_cfg(m, ntiles);
+    const LmNormalPlan pl = plan_for(m, n);
+    if (row_begin < 0 || row_end > pl.nt || row_begin >= row_end) return PNOL_ERR_ARG;
     const int t0 = row_begin * (row_begin + 1) / 2, t1 = row_end * (row_end + 1) / 2;
-    const size_t per_tile = (size_t)kS * sc.sub * kTile * kTile;
-    void* part = nullptr;
-    ctx->lm_trip_tiles.kind = 0;   // the trip's tiles are overwritten below
-    PNOL_CHECK(ws_get(ctx, "syrk_part", sizeof(double) * (size_t)ntiles * per_tile, &part));
-    double* mypart = (double*)part + (size_t)t0 * per_tile;   // disjoint per row range
-    syrk_partials(ctx, stream, true, JT, ldjt, sc.mS, n, m, sc, 0, kS, t0, t1 - t0, mypart);
+    double* part = nullptr;
+    PNOL_CHECK(part_ws(ctx, pl.part_elems(), &part));
+    double* mypart = part + (size_t)t0 * pl.per_tile;   // disjoint per row range
+    syrk_partials(ctx, stream, true, JT, ldjt, pl.sc.mS, pl, 0, kS, t0, t1 - t0, mypart);
     PNOL_CHECK(launch_check());
-    launch_reduce(dim3(kTile / 32, t1 - t0), dim3(256), 0, stream, (const double*)mypart, t1 - t0,
-                       sc.sub, n, lambda, A, (long)lda, jtj_diag, t0);
+    launch_reduce(stream, pl, mypart, t0, t1 - t0, lambda, A, lda, jtj_diag);
     return launch_check();
 }
 
@@ -907,83 +895,57 @@ int launch_fd_normal_solve(pnol_ctx* ctx, pnol_dobj* o, const double* x, const d
     if (!o || !x || !h || !F0 || !JT || !rhs || !sigma || !dinfo || !xnext || ldjt < o->m) return PNOL_ERR_ARG;
     const int n = o->n, m = o->m;
     if (n <= PNOL_SEQ_MAX) return PNOL_ERR_ARG;
-    const int nt = (n + kTile - 1) / kTile;
-    const int ntiles = nt * (nt + 1) / 2;
-    const SliceCfg sc = slice_cfg(m, ntiles);
-    const int split = kS * sc.sub;
+    const LmNormalPlan pl = plan_for(m, n);
+    const SliceCfg& sc = pl.sc;
+    const int ntiles = pl.ntiles;
     // the reduce (PNOL_LM_REDUCE, read per call): "tail" (default) its workgroups in the SYRK's
     // own launch (k_syrk_red), taking the slots of the SYRK's last dispatch round -- 3 of 3
     // same-box bench pairs faster than "launch", a reduce launch of its own writing the
     // Cholesky's padded matrix and b (1.18-1.20 ms for both against 1.14-1.16 + 0.07); "tasks":
     // the persistent launch's first tasks (round 4).  PNOL_SYRK_RED_SC1=1: write-through partials
     // and no release fence in the tail form (the same speed).
-    const char* er = std::getenv("PNOL_LM_REDUCE");
-    const bool tasks = er && std::strcmp(er, "tasks") == 0;
-    const bool tail = (!er || std::strcmp(er, "tail") == 0) && !syrk_t64(false);
+    const bool tasks = env_equals("PNOL_LM_REDUCE", "tasks");
+    const bool tail = env_equals("PNOL_LM_REDUCE", "tail", true) && !syrk_t64(false);
     // every workspace first: a (re)allocation frees, and a free waits for the device
-    void *part = nullptr, *jp = nullptr;
-    ctx->lm_trip_tiles.kind = 0;   // the trip's tiles are overwritten below
-    PNOL_CHECK(ws_get(ctx, "syrk_part", sizeof(double) * (size_t)ntiles * split * kTile * kTile, &part));
-    PNOL_CHECK(ws_get(ctx, "jtr_part", sizeof(double) * (size_t)kS * n, &jp));
+    double *part = nullptr, *jp = nullptr;
+    PNOL_CHECK(part_ws(ctx, pl.part_elems(), &part));
+    PNOL_CHECK(jtr_ws(ctx, pl, &jp));
     void* tcnt = nullptr;
     if (tail) PNOL_CHECK(ws_get(ctx, "syrk_tcnt", sizeof(int) * (size_t)ntiles, &tcnt));
     CholRed cr;
     PNOL_CHECK(launch_chol_reducing_prep(ctx, n, dinfo, cr));
     if (fd_queued) PNOL_CHECK(lm_fd_commit(ctx, o, x));   // the Jacobian at x is queued already
     else PNOL_CHECK(launch_fd_jacobian(ctx, o, x, h, 0, n, F0, compute_f0, JT, ldjt));
-    PNOL_CHECK(jtr_gemv(ctx, JT, ldjt, sc.mS, m, n, sc.mS, 0, kS, F0));
+    PNOL_CHECK(jtr_gemv(ctx, pl, JT, ldjt, sc.mS, F0));
     // the prep launch (words, paddings, info; the tile counters)
     PNOL_CHECK(launch_chol_reducing_start(ctx, cr, !tasks, (int*)tcnt, ntiles));
     if (tail) {
-        const int nsyrk = ntiles * split, nred = (kTile / kRedSR) * (ntiles + 1);
-        const char* es = std::getenv("PNOL_SYRK_RED_SC1");
-        const bool sc1 = es && std::atoi(es) != 0;
+        const int nsyrk = ntiles * pl.split, nred = (kTile / kRedSR) * (ntiles + 1);
+        const bool sc1 = env_atoi("PNOL_SYRK_RED_SC1", 0) != 0;
         // the diagonal tiles last (default; PNOL_SYRK_DLAST=0 keeps the row order, read per call):
         // FETCH 1.75 -> 1.39 GB per launch at the same speed (3 same-box pairs, PMC passes of both)
-        const char* ed = std::getenv("PNOL_SYRK_DLAST");
-        const bool dlast = !ed || std::atoi(ed) != 0;
-        {
-            LaunchTimer tm(ctx, "syrk");
-#define PNOL_RED(SB, SC, DL)                                                                                          \
-    hipExtLaunchKernelGGL((k_syrk_red<SB, SC, DL>), dim3(nsyrk + nred), dim3(512), 0, ctx->stream, tm.start(), tm.stop(), 0, \
-                          JT, (long)ldjt, n, m, split, sc.kfirst, sc.kchunk, sc.sub, sc.mS, (long)sc.mS, (double*)part,   \
-                          nsyrk, (int*)tcnt, ntiles, n, lambda, cr.w.P, cr.w.ldp, (const double*)jp, rhs, cr.w.bv,       \
-                          cr.dinfo)
-            if (sc.sub == 2) {
-                if (dlast) {
-                    if (sc1) PNOL_RED(2, true, true); else PNOL_RED(2, false, true);
-                } else {
-                    if (sc1) PNOL_RED(2, true, false); else PNOL_RED(2, false, false);
-                }
-            } else {
-                if (sc1) PNOL_RED(0, true, false); else PNOL_RED(0, false, false);
-            }
-#undef PNOL_RED
-        }
+        const bool dlast = env_default_on("PNOL_SYRK_DLAST");
+        LaunchTimer tm(ctx, "syrk");
+        hipExtLaunchKernelGGL(syrk_red_kernel(sc.sub, sc1, dlast), dim3(nsyrk + nred), dim3(512), 0, ctx->stream,
+                              tm.start(), tm.stop(), 0, JT, (long)ldjt, n, m, pl.split, sc.kfirst, sc.kchunk, sc.sub,
+                              sc.mS, (long)sc.mS, part, nsyrk, (int*)tcnt, ntiles, n, lambda, cr.w.P, cr.w.ldp,
+                              (const double*)jp, rhs, cr.w.bv, cr.dinfo);
         PNOL_CHECK(launch_check());
-        ScopedTimer tm(ctx, "solve");
-        PNOL_CHECK(launch_chol_preloaded_run(ctx, ctx->stream, cr, sigma, x, xnext));
-        ctx->lm_trip_tiles = {1, m, n, 1};
-        return PNOL_OK;
-    }
-    syrk_partials(ctx, ctx->stream, false, JT, ldjt, sc.mS, n, m, sc, 0, kS, 0, ntiles, (double*)part,
-                  syrk_t64(false));
-    PNOL_CHECK(launch_check());
-    if (!tasks) {
-        {   // A (Marquardt diagonal, mirror) straight into the padded matrix, rhs into rhs and b
+    } else {
+        syrk_partials(ctx, ctx->stream, false, JT, ldjt, sc.mS, pl, 0, kS, 0, ntiles, part, syrk_t64(false));
+        PNOL_CHECK(launch_check());
+        if (!tasks) {   // A (Marquardt diagonal, mirror) straight into the padded matrix, rhs into rhs and b
             ScopedTimer tm(ctx, "syrk_reduce");
-            launch_reduce(dim3(kTile / 32, ntiles + 1), dim3(256), 0, ctx->stream, (const double*)part, ntiles, sc.sub,
-                          n, lambda, cr.w.P, cr.w.ldp, (double*)nullptr, 0, (const double*)jp, rhs, cr.w.bv);
+            launch_reduce(ctx->stream, pl, part, 0, ntiles, lambda, cr.w.P, cr.w.ldp, nullptr, jp, rhs, cr.w.bv);
             PNOL_CHECK(launch_check());
         }
-        ScopedTimer tm(ctx, "solve");
-        PNOL_CHECK(launch_chol_preloaded_run(ctx, ctx->stream, cr, sigma, x, xnext));
-    } else {
-        ScopedTimer tm(ctx, "solve");
-        PNOL_CHECK(launch_chol_reducing_run(ctx, ctx->stream, cr, (const double*)part, sc.sub, (const double*)jp,
-                                            lambda, rhs, sigma, x, xnext));
     }
-    ctx->lm_trip_tiles = {1, m, n, 1};   // pnol_lm_trip_normal_d may form A from these partials
+    ScopedTimer tm(ctx, "solve");
+    if (!tasks)
+        PNOL_CHECK(launch_chol_preloaded_run(ctx, ctx->stream, cr, sigma, x, xnext));
+    else
+        PNOL_CHECK(launch_chol_reducing_run(ctx, ctx->stream, cr, part, sc.sub, jp, lambda, rhs, sigma, x, xnext));
+    trip_tiles_left(ctx, pl, 1);   // pnol_lm_trip_normal_d may form A from these partials
     return PNOL_OK;
 }
 
@@ -991,17 +953,13 @@ int launch_fd_normal_solve(pnol_ctx* ctx, pnol_dobj* o, const double* x, const d
 // launch_fd_normal_solve (the same reduce as launch_jtj, so the same A)
 int launch_jtj_from_partials(pnol_ctx* ctx, int m, int n, double lambda, double* A, int lda) {
     if (!A || m <= 0 || n <= PNOL_SEQ_MAX || lda < n) return PNOL_ERR_ARG;
-    // the partials must still be the last trip's, of this shape (any other J^T J call since
-    // overwrote them)
+    // the partials must still be the last trip's, of this shape (any other J^T J call since overwrote them)
     const auto& tt = ctx->lm_trip_tiles;
     if (tt.kind != 1 || tt.m != m || tt.n != n || tt.nranks != 1) return PNOL_ERR_ARG;
-    const int nt = (n + kTile - 1) / kTile;
-    const int ntiles = nt * (nt + 1) / 2;
-    const SliceCfg sc = slice_cfg(m, ntiles);
-    void* part = nullptr;
-    PNOL_CHECK(ws_get(ctx, "syrk_part", sizeof(double) * (size_t)ntiles * kS * sc.sub * kTile * kTile, &part));
-    launch_reduce(dim3(kTile / 32, ntiles), dim3(256), 0, ctx->stream, (const double*)part, ntiles, sc.sub, n, lambda,
-                  A, (long)lda, (double*)nullptr, 0);
+    const LmNormalPlan pl = plan_for(m, n);
+    double* part = nullptr;
+    PNOL_CHECK(part_ws(ctx, pl.part_elems(), &part, true));
+    launch_reduce(ctx->stream, pl, part, 0, pl.ntiles, lambda, A, lda, nullptr);
     return launch_check();
 }
 
@@ -1014,73 +972,31 @@ int launch_jtj_sharded(pnol_ctx* ctx, const double* JT, int ldjt, int m, int n, 
     const int P = comm_size(), rank = comm_rank();
     if (P <= 1 || (n <= PNOL_SEQ_MAX && m <= 4096)) return launch_jtj(ctx, JT, ldjt, m, n, lambda, A, lda, jtj_diag);
     if (!JT || !A || m <= 0 || n <= 0 || ldjt < m || lda < n) return PNOL_ERR_ARG;
-    const int nt = (n + kTile - 1) / kTile;
-    const int ntiles = nt * (nt + 1) / 2;
-    const SliceCfg sc = slice_cfg(m, ntiles);
-    const int tpr = (ntiles + P - 1) / P;
-    const int t0 = std::min(ntiles, rank * tpr), cnt = std::min(ntiles, t0 + tpr) - t0;
-    const size_t E = (size_t)kTile * kTile;
-    void *part = nullptr, *packed = nullptr;
-    ctx->lm_trip_tiles.kind = 0;   // the trip's tiles are overwritten below
-    PNOL_CHECK(ws_get(ctx, "syrk_part", sizeof(double) * (size_t)std::max(cnt, 1) * kS * sc.sub * E, &part));
-    PNOL_CHECK(ws_get(ctx, "syrk_packed", sizeof(double) * (size_t)P * tpr * E, &packed));
-    double* mine = (double*)packed + (size_t)rank * tpr * E;
+    const LmNormalPlan pl = plan_for(m, n, P, rank);
+    const int t0 = pl.t0_of(rank), cnt = pl.cnt_of(rank);
+    const long tiles = pl.jtf_off();   // a slot of tiles alone: tpr * 128^2 doubles
+    double *part = nullptr, *packed = nullptr;
+    PNOL_CHECK(part_ws(ctx, pl.part_elems(cnt, kS), &part));
+    PNOL_CHECK(ws_get(ctx, "syrk_packed", sizeof(double) * (size_t)P * tiles, (void**)&packed));
+    double* mine = packed + (size_t)rank * tiles;
     if (cnt > 0) {
-        syrk_partials(ctx, ctx->stream, false, JT, ldjt, sc.mS, n, m, sc, 0, kS, t0, cnt, (double*)part);
+        syrk_partials(ctx, ctx->stream, false, JT, ldjt, pl.sc.mS, pl, 0, kS, t0, cnt, part);
         PNOL_CHECK(launch_check());
-        hipLaunchKernelGGL(k_syrk_reduce_packed, dim3(8, cnt), dim3(256), 0, ctx->stream, (const double*)part, sc.sub,
-                           mine);
+        hipLaunchKernelGGL(k_syrk_reduce_packed, dim3(8, cnt), dim3(256), 0, ctx->stream, (const double*)part,
+                           pl.sc.sub, mine);
         PNOL_CHECK(launch_check());
     }
-    PNOL_CHECK(comm_allgather_device(ctx, mine, (double*)packed, (size_t)tpr * E));
+    PNOL_CHECK(comm_allgather_device(ctx, mine, packed, (size_t)tiles));
     ScopedTimer tm(ctx, "syrk_reduce");
-    hipLaunchKernelGGL(k_syrk_unpack, dim3(8, ntiles), dim3(256), 0, ctx->stream, (const double*)packed, ntiles, n,
-                       lambda, (long)tpr * E, tpr, A, (long)lda, jtj_diag);
-    return launch_check();
-}
-
-// The dyadic nodes of the slice tree inside [a, b), in slice order: (first slice, width).
-static void dyadic_nodes(int a, int b, std::vector<std::pair<int, int>>& out) {
-    out.clear();
-    int i = a;
-    while (i < b) {
-        int w = 1;
-        while (i % (2 * w) == 0 && i + 2 * w <= b && 2 * w <= kS) w *= 2;
-        out.push_back({i, w});
-        i += w;
-    }
-}
-
-// -J^T F on the m-slices [s0, s0 + nsl): jp[(s - s0) * n + j] = -sum_{k in slice s} JT_jk F_k
-// (JT slice s at JT + s * sstride, row stride ldjt), then the slice nodes of that range into
-// out[c * n + j] (one node = -J^T F itself when the range is all kLmSlices slices).
-static int jtr_gemv(pnol_ctx* ctx, const double* JT, int ldjt, long sstride, int m, int n, int mS, int s0, int nsl,
-                    const double* F, hipStream_t stream) {
-    if (!F) return PNOL_ERR_ARG;
-    void* jp = nullptr;
-    PNOL_CHECK(ws_get(ctx, "jtr_part", sizeof(double) * (size_t)kS * n, &jp));
-    return launch_gemv_neg_slices(ctx, JT, ldjt, sstride, n, m, mS, s0, nsl, F, (double*)jp, stream);
-}
-
-static int jtr_tree(pnol_ctx* ctx, int n, int s0, int nsl, double* out) {
-    void* jp = nullptr;
-    PNOL_CHECK(ws_get(ctx, "jtr_part", sizeof(double) * (size_t)kS * n, &jp));
-    hipLaunchKernelGGL(k_tree_nodes, dim3((n + 255) / 256, 1), dim3(256), 0, ctx->stream, (const double*)jp, 0L,
-                       (long)n, 1, s0, s0 + nsl, n, out, (long)n, 0L);
-    return launch_check();
-}
-
-static int jtr_slices(pnol_ctx* ctx, const double* JT, int ldjt, long sstride, int m, int n, int mS, int s0, int nsl,
-                      const double* F, double* out) {
-    PNOL_CHECK(jtr_gemv(ctx, JT, ldjt, sstride, m, n, mS, s0, nsl, F));
-    return jtr_tree(ctx, n, s0, nsl, out);
+    return launch_unpack(ctx, pl, packed, tiles, lambda, A, lda, jtj_diag);
 }
 
 int launch_jtr(pnol_ctx* ctx, const double* JT, int ldjt, int m, int n, const double* F, double* rhs) {
     if (n <= PNOL_SEQ_MAX && m <= 4096) return launch_gemv_neg_seq(ctx, JT, ldjt, n, m, F, rhs);
     if (!JT || !F || !rhs || m <= 0 || n <= 0 || ldjt < m) return PNOL_ERR_ARG;
-    const int mS = lm_slice_rows(m);
-    return jtr_slices(ctx, JT, ldjt, mS, m, n, mS, 0, kS, F, rhs);
+    const LmNormalPlan pl = plan_for(m, n);
+    PNOL_CHECK(jtr_gemv(ctx, pl, JT, ldjt, pl.sc.mS, F));
+    return jtr_tree(ctx, pl, rhs);
 }
 
 // LevMarqMPI normal equations on the m-sliced Jacobian (layout of pnol_lm_sliced_layout):
@@ -1092,146 +1008,103 @@ int launch_jtr(pnol_ctx* ctx, const double* JT, int ldjt, int m, int n, const do
 //   3. the owner merges the nodes of its tiles; one allgather of (owned tiles + this rank's
 //      -J^T F nodes); every rank unpacks A and merges -J^T F.
 // Bitwise equal to launch_jtj + launch_jtr on the row-major J^T for every P <= kLmSlices.
-// where launch_lm_normal left the summed tiles when asked not to unpack them (A == nullptr)
-struct LmTiles {
-    bool partials = false;   // one rank: the split-K partials ("syrk_part") and -J^T F partials ("jtr_part")
-    const double* part = nullptr;
-    const double* jp = nullptr;
-    int sub = 0, split = 0;
-    const double* packed = nullptr;   // several ranks: the allgathered tiles
-    long slot = 0;
-    int tpr = 1;
+// LmWork: the call's plan and buffers; without A (the reducing Cholesky sums the tiles itself) what
+// launch_lm_normal_solve reads: one rank (partials) "syrk_part" and "jtr_part", else "lm_packed"
+struct LmWork {
+    LmNormalPlan pl;
+    double *part = nullptr, *jp = nullptr, *nodes = nullptr, *recv = nullptr, *packed = nullptr;
+    bool partials = false;
+    double* mine() const { return packed + pl.slot_off(pl.rank); }   // my allgather slot
 };
 
-static int lm_normal_core(pnol_ctx* ctx, const double* JTs, int m, int n, double lambda, const double* F, double* A,
-                          int lda, double* rhs, double* jtj_diag, LmTiles* out) {
-    if (!JTs || !F || !rhs || m <= 0 || n <= 0 || (A && lda < n) || (!A && !out)) return PNOL_ERR_ARG;
-    if (n <= PNOL_SEQ_MAX && m <= 4096) return PNOL_ERR_UNSUPPORTED;   // reference-order kernels: row-major J^T
-    const int P = comm_size(), me = comm_rank();
-    if (P > kS) return PNOL_ERR_UNSUPPORTED;
-    const int nt = (n + kTile - 1) / kTile;
-    const int ntiles = nt * (nt + 1) / 2;
-    const SliceCfg sc = slice_cfg(m, ntiles);
-    const long sstr = (long)n * sc.mS;
-    const long E = (long)kTile * kTile;
-    int s0, s1;
-    lm_rank_slices(P, me, &s0, &s1);
-    const int nsl = s1 - s0;
-    void* part = nullptr;
-    ctx->lm_trip_tiles.kind = 0;   // the trip's tiles are overwritten below
-    PNOL_CHECK(ws_get(ctx, "syrk_part", sizeof(double) * (size_t)ntiles * std::max(nsl, 1) * sc.sub * E, &part));
-    const bool t64 = syrk_t64(true);
-    if (nsl > 0) {
-        syrk_partials(ctx, ctx->stream, false, JTs, sc.mS, sstr, n, m, sc, s0, nsl, 0, ntiles, (double*)part, t64);
-        PNOL_CHECK(launch_check());
-        PNOL_CHECK(jtr_gemv(ctx, JTs, sc.mS, sstr, m, n, sc.mS, s0, nsl, F));
-    }
-    if (P == 1) {
-        // the -J^T F tree rides in the reduce launch
-        void* jp = nullptr;
-        PNOL_CHECK(ws_get(ctx, "jtr_part", sizeof(double) * (size_t)kS * n, &jp));
-        if (!A) {   // the reducing Cholesky sums the partials itself
-            out->partials = true;
-            out->part = (const double*)part;
-            out->jp = (const double*)jp;
-            out->sub = sc.sub;
-            out->split = kS * sc.sub;
-            return PNOL_OK;
-        }
-        {
-            ScopedTimer tm(ctx, "syrk_reduce");
-            launch_reduce(dim3(kTile / 32, ntiles + 1), dim3(256), 0, ctx->stream, (const double*)part, ntiles,
-                          sc.sub, n, lambda, A, (long)lda, jtj_diag, 0, (const double*)jp, rhs);
-        }
-        return launch_check();
-    }
-    // the global node list: rank q's nodes in slice order, ranks in order
-    std::vector<std::pair<int, int>> nodes;
-    std::vector<int> owner, first(P + 1, 0);
-    for (int q = 0; q < P; ++q) {
-        int a, b;
-        lm_rank_slices(P, q, &a, &b);
-        std::vector<std::pair<int, int>> nq;
-        dyadic_nodes(a, b, nq);
-        first[q] = (int)nodes.size();
-        for (auto& nd : nq) {
-            nodes.push_back(nd);
-            owner.push_back(q);
-        }
-    }
-    first[P] = (int)nodes.size();
-    const int NC = (int)nodes.size(), nn = first[me + 1] - first[me];
-    constexpr int kMaxNodes = 4;   // dyadic nodes of a slice range of an 8-leaf tree
-    const int tpr = (ntiles + P - 1) / P;
-    auto t0_of = [&](int d) { return std::min(ntiles, d * tpr); };
-    auto cnt_of = [&](int d) { return std::min(ntiles, t0_of(d) + tpr) - t0_of(d); };
-    const long slot = (long)tpr * E + (long)kMaxNodes * n;
-    void *nodebuf = nullptr, *recv = nullptr, *packed = nullptr;
-    PNOL_CHECK(ws_get(ctx, "lm_nodes", sizeof(double) * (size_t)std::max(nn, 1) * ntiles * E, &nodebuf));
-    PNOL_CHECK(ws_get(ctx, "lm_nodes_recv", sizeof(double) * (size_t)NC * tpr * E, &recv));
-    PNOL_CHECK(ws_get(ctx, "lm_packed", sizeof(double) * (size_t)P * slot, &packed));
-    double* mine = (double*)packed + (size_t)me * slot;
-    if (nsl > 0) {
+// step 1: this rank's partial tiles of J^T J (all tiles) and its -J^T F partials, over its slices
+static int lm_local_partials(pnol_ctx* ctx, LmWork& w, const double* JTs, const double* F) {
+    const LmNormalPlan& pl = w.pl;
+    const long sstr = (long)pl.n * pl.sc.mS;
+    PNOL_CHECK(part_ws(ctx, pl.part_elems(pl.ntiles, pl.nsl()), &w.part));
+    if (pl.nsl() == 0) return PNOL_OK;
+    syrk_partials(ctx, ctx->stream, false, JTs, pl.sc.mS, sstr, pl, pl.s0, pl.nsl(), 0, pl.ntiles, w.part,
+                  syrk_t64(true));
+    PNOL_CHECK(launch_check());
+    return jtr_gemv(ctx, pl, JTs, pl.sc.mS, sstr, F);
+}
+
+// step 2, one rank: the reduce into A, the -J^T F tree riding in its launch (without A: nothing to do)
+static int lm_one_rank_finish(pnol_ctx* ctx, LmWork& w, double lambda, double* A, int lda, double* rhs,
+                              double* jtj_diag) {
+    PNOL_CHECK(jtr_ws(ctx, w.pl, &w.jp));
+    w.partials = !A;
+    if (!A) return PNOL_OK;
+    ScopedTimer tm(ctx, "syrk_reduce");
+    launch_reduce(ctx->stream, w.pl, w.part, 0, w.pl.ntiles, lambda, A, lda, jtj_diag, w.jp, rhs);
+    return launch_check();
+}
+
+// step 3: my slice-tree nodes of every tile, my -J^T F nodes into the tail of my allgather slot,
+// then the reduce-scatter in tree order: rank q's nodes of owner d's tiles -> d
+static int lm_nodes_exchange(pnol_ctx* ctx, const LmWork& w) {
+    const LmNormalPlan& pl = w.pl;
+    constexpr long E = LmNormalPlan::E;
+    if (pl.nsl() > 0) {
         ScopedTimer tm(ctx, "syrk_reduce");
-        hipLaunchKernelGGL(k_tree_nodes, dim3(kTile * kTile / 256 / 4, ntiles), dim3(256), 0, ctx->stream,
-                           (const double*)part, (long)nsl * sc.sub * E, E, sc.sub, s0, s1, (int)E,
-                           (double*)nodebuf, (long)ntiles * E, E);
+        hipLaunchKernelGGL(k_tree_nodes, dim3(kTile * kTile / 256 / 4, pl.ntiles), dim3(256), 0, ctx->stream,
+                           (const double*)w.part, (long)pl.nsl() * pl.sc.sub * E, E, pl.sc.sub, pl.s0, pl.s1, (int)E,
+                           w.nodes, (long)pl.ntiles * E, E);
     }
     PNOL_CHECK(launch_check());
-    // -J^T F nodes of my slices into the tail of my allgather slot
-    if (nsl > 0) PNOL_CHECK(jtr_tree(ctx, n, s0, nsl, mine + (long)tpr * E));
-    // reduce-scatter in tree order: rank q's nodes of owner d's tiles -> d
-    {
-        ScopedTimer tm(ctx, "exchange_A");
-        PNOL_CHECK(comm_exchange(ctx, (const double*)nodebuf, (double*)recv, [&](int q, int d, std::vector<XBlock>& bl) {
-            bl.clear();
-            if (cnt_of(d) == 0) return;
-            for (int c = first[q]; c < first[q + 1]; ++c)
-                bl.push_back({(size_t)((c - first[q]) * (long)ntiles + t0_of(d)) * E, (size_t)c * tpr * E,
-                              (size_t)cnt_of(d) * E});
-        }));
-    }
-    if (cnt_of(me) > 0) {
-        TreeNodes tn{};
-        for (int c = 0; c < NC; ++c) {
-            const int lo = nodes[c].first;
-            tn.w[lo] = nodes[c].second;
-            tn.p[lo] = owner[c] == me ? (const double*)nodebuf + ((long)(c - first[me]) * ntiles + t0_of(me)) * E
-                                      : (const double*)recv + (long)c * tpr * E;
-        }
-        ScopedTimer tm(ctx, "syrk_reduce");
-        const long el = (long)cnt_of(me) * E;
-        hipLaunchKernelGGL(k_tree_combine, dim3((unsigned)std::min<long>((el + 255) / 256, 4096)), dim3(256), 0,
-                           ctx->stream, tn, el, mine);
-        PNOL_CHECK(launch_check());
-    }
-    PNOL_CHECK(comm_allgather_device(ctx, mine, (double*)packed, (size_t)slot));
-    {
-        ScopedTimer tm(ctx, "syrk_reduce");
-        if (A) {
-            hipLaunchKernelGGL(k_syrk_unpack, dim3(8, ntiles), dim3(256), 0, ctx->stream, (const double*)packed, ntiles,
-                               n, lambda, slot, tpr, A, (long)lda, jtj_diag);
-            PNOL_CHECK(launch_check());
-        } else {   // the reducing Cholesky reads the tiles itself
-            out->packed = (const double*)packed;
-            out->slot = slot;
-            out->tpr = tpr;
-        }
-        TreeNodes tr{};
-        for (int c = 0; c < NC; ++c) {
-            const int lo = nodes[c].first;
-            tr.w[lo] = nodes[c].second;
-            tr.p[lo] = (const double*)packed + (long)owner[c] * slot + (long)tpr * E + (long)(c - first[owner[c]]) * n;
-        }
-        hipLaunchKernelGGL(k_tree_combine, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, tr, (long)n, rhs);
-    }
+    if (pl.nsl() > 0) PNOL_CHECK(jtr_tree(ctx, pl, w.mine() + pl.jtf_off()));
+    ScopedTimer tm(ctx, "exchange_A");
+    return comm_exchange(ctx, w.nodes, w.recv, [&](int q, int d, std::vector<XBlock>& bl) {
+        bl.clear();
+        pl.exchange_blocks(q, d, [&](const XBlock& b) { bl.push_back(b); });
+    });
+}
+
+// step 4: the owner merges the nodes of its tiles into the head of its allgather slot
+static int lm_owner_merge(pnol_ctx* ctx, const LmWork& w) {
+    const LmNormalPlan& pl = w.pl;
+    const long el = (long)pl.cnt_of(pl.rank) * LmNormalPlan::E;
+    if (el == 0) return PNOL_OK;
+    const auto tn = tree_table(pl, [&](int c) { return (pl.merge_local(c) ? w.nodes : w.recv) + pl.merge_off(c); });
+    ScopedTimer tm(ctx, "syrk_reduce");
+    hipLaunchKernelGGL(k_tree_combine, dim3((unsigned)std::min<long>((el + 255) / 256, 4096)), dim3(256), 0,
+                       ctx->stream, tn, el, w.mine());
     return launch_check();
+}
+
+// step 5: one allgather of (owned tiles + this rank's -J^T F nodes); every rank unpacks A -- or,
+// without A, leaves the tiles packed -- and merges -J^T F
+static int lm_gather_finish(pnol_ctx* ctx, const LmWork& w, double lambda, double* A, int lda, double* rhs,
+                            double* jtj_diag) {
+    const LmNormalPlan& pl = w.pl;
+    PNOL_CHECK(comm_allgather_device(ctx, w.mine(), w.packed, (size_t)pl.slot));
+    ScopedTimer tm(ctx, "syrk_reduce");
+    if (A) PNOL_CHECK(launch_unpack(ctx, pl, w.packed, pl.slot, lambda, A, lda, jtj_diag));
+    const TreeNodes tr = tree_table(pl, [&](int c) { return (const double*)w.packed + pl.jtf_node_off(c); });
+    hipLaunchKernelGGL(k_tree_combine, dim3((pl.n + 255) / 256), dim3(256), 0, ctx->stream, tr, (long)pl.n, rhs);
+    return launch_check();
+}
+
+static int lm_normal_core(pnol_ctx* ctx, const double* JTs, int m, int n, double lambda, const double* F, double* A,
+                          int lda, double* rhs, double* jtj_diag, LmWork& w) {
+    if (!JTs || !F || !rhs || m <= 0 || n <= 0 || (A && lda < n)) return PNOL_ERR_ARG;
+    if (n <= PNOL_SEQ_MAX && m <= 4096) return PNOL_ERR_UNSUPPORTED;   // reference-order kernels: row-major J^T
+    w.pl = plan_for(m, n, comm_size(), comm_rank());
+    if (!w.pl.ok) return PNOL_ERR_UNSUPPORTED;   // more ranks than m-slices
+    PNOL_CHECK(lm_local_partials(ctx, w, JTs, F));
+    if (w.pl.P == 1) return lm_one_rank_finish(ctx, w, lambda, A, lda, rhs, jtj_diag);
+    PNOL_CHECK(ws_get(ctx, "lm_nodes", sizeof(double) * w.pl.nodes_elems(), (void**)&w.nodes));
+    PNOL_CHECK(ws_get(ctx, "lm_nodes_recv", sizeof(double) * w.pl.recv_elems(), (void**)&w.recv));
+    PNOL_CHECK(packed_ws(ctx, w.pl, &w.packed));
+    PNOL_CHECK(lm_nodes_exchange(ctx, w));
+    PNOL_CHECK(lm_owner_merge(ctx, w));
+    return lm_gather_finish(ctx, w, lambda, A, lda, rhs, jtj_diag);
 }
 
 int launch_lm_normal(pnol_ctx* ctx, const double* JTs, int m, int n, double lambda, const double* F, double* A,
                      int lda, double* rhs, double* jtj_diag) {
-    if (!A) return PNOL_ERR_ARG;
-    return lm_normal_core(ctx, JTs, m, n, lambda, F, A, lda, rhs, jtj_diag, nullptr);
+    LmWork w;
+    return A ? lm_normal_core(ctx, JTs, m, n, lambda, F, A, lda, rhs, jtj_diag, w) : PNOL_ERR_ARG;
 }
 
 // LevMarqMPI's normal equations and damped solve without forming A: the tiles of
@@ -1244,18 +1117,17 @@ int launch_lm_normal_solve(pnol_ctx* ctx, const double* JTs, int m, int n, doubl
     if (!sigma || !dinfo || !xnext || n <= PNOL_SEQ_MAX) return PNOL_ERR_ARG;
     CholRed cr;
     PNOL_CHECK(launch_chol_reducing_prep(ctx, n, dinfo, cr));
-    LmTiles tl;
-    PNOL_CHECK(lm_normal_core(ctx, JTs, m, n, lambda, F, nullptr, 0, rhs, nullptr, &tl));
+    LmWork tl;
+    PNOL_CHECK(lm_normal_core(ctx, JTs, m, n, lambda, F, nullptr, 0, rhs, nullptr, tl));
     PNOL_CHECK(launch_chol_reducing_start(ctx, cr));
     ScopedTimer tm(ctx, "solve");
     if (tl.partials)
-        PNOL_CHECK(launch_chol_reducing_run(ctx, ctx->stream, cr, tl.part, tl.sub, tl.jp, lambda, rhs, sigma, xbase,
-                                            xnext));
+        PNOL_CHECK(launch_chol_reducing_run(ctx, ctx->stream, cr, tl.part, tl.pl.sc.sub, tl.jp, lambda, rhs, sigma,
+                                            xbase, xnext));
     else
-        PNOL_CHECK(launch_chol_reducing_run_packed(ctx, ctx->stream, cr, tl.packed, tl.slot, tl.tpr, rhs, lambda, sigma,
-                                                   xbase, xnext));
-    // pnol_lm_normal_unpack_mpi_d may form A from these tiles
-    ctx->lm_trip_tiles = {tl.partials ? 1 : 2, m, n, comm_size()};
+        PNOL_CHECK(launch_chol_reducing_run_packed(ctx, ctx->stream, cr, tl.packed, tl.pl.slot, tl.pl.tpr, rhs, lambda,
+                                                   sigma, xbase, xnext));
+    trip_tiles_left(ctx, tl.pl, tl.partials ? 1 : 2);   // pnol_lm_normal_unpack_mpi_d may form A from these tiles
     return PNOL_OK;
 }
 
@@ -1267,17 +1139,10 @@ int launch_lm_normal_unpack(pnol_ctx* ctx, int m, int n, double lambda, double* 
     if (P == 1) return launch_jtj_from_partials(ctx, m, n, lambda, A, lda);
     const auto& tt = ctx->lm_trip_tiles;   // the last trip's allgathered tiles, of this shape
     if (tt.kind != 2 || tt.m != m || tt.n != n || tt.nranks != P) return PNOL_ERR_ARG;
-    const int nt = (n + kTile - 1) / kTile;
-    const int ntiles = nt * (nt + 1) / 2;
-    const long E = (long)kTile * kTile;
-    const int tpr = (ntiles + P - 1) / P;
-    constexpr int kMaxNodes = 4;
-    const long slot = (long)tpr * E + (long)kMaxNodes * n;
-    void* packed = nullptr;
-    PNOL_CHECK(ws_get(ctx, "lm_packed", sizeof(double) * (size_t)P * slot, &packed));
-    hipLaunchKernelGGL(k_syrk_unpack, dim3(8, ntiles), dim3(256), 0, ctx->stream, (const double*)packed, ntiles, n,
-                       lambda, slot, tpr, A, (long)lda, (double*)nullptr);
-    return launch_check();
+    const LmNormalPlan pl = plan_for(m, n, P, comm_rank());   // the layout lm_normal_core wrote
+    double* packed = nullptr;
+    PNOL_CHECK(packed_ws(ctx, pl, &packed));
+    return launch_unpack(ctx, pl, packed, pl.slot, lambda, A, lda, nullptr);
 }
 
 }  // namespace pnol

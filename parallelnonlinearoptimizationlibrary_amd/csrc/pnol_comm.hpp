@@ -5,6 +5,7 @@
 #include <functional>
 #include <vector>
 
+#include "lm_normal_plan.hpp"
 #include "pnol_amd.h"
 
 namespace pnol {
@@ -36,10 +37,7 @@ int comm_allgather_int(pnol_ctx* ctx, int mine, std::vector<int>& all);
 // rank dst (src != dst) -- soff into the sender's sbase, roff into the receiver's rbase, count
 // doubles -- and must give the same list on every rank.  RCCL: one group of sends / receives
 // on `stream` (nullptr: the context stream); host backend: packed through one allgather, the
-// copies on `stream` (the host waits for that stream only).
-struct XBlock {
-    size_t soff, roff, count;
-};
+// copies on `stream` (the host waits for that stream only).  (XBlock: lm_normal_plan.hpp)
 int comm_exchange(pnol_ctx* ctx, const double* sbase, double* rbase,
                   const std::function<void(int, int, std::vector<XBlock>&)>& blocks, void* stream = nullptr);
 // process default GPU context (nullptr when no gfx950 device is visible)

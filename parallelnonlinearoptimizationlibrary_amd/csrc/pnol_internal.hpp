@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "lm_normal_plan.hpp"
 #include "pnol_amd.h"
 
 namespace pnol {
@@ -106,7 +107,8 @@ struct pnol_ctx {
     // What the last LM trip without A (launch_fd_normal_solve / launch_lm_normal_solve) left for
     // its A-forming entry points (pnol_lm_trip_normal_d, pnol_lm_normal_unpack_mpi_d): the
     // split-K partials ("syrk_part", kind 1) or the allgathered tiles ("lm_packed", kind 2) of
-    // shape (m, n) over nranks ranks.  Every other writer of those buffers clears it.
+    // shape (m, n) over nranks ranks.  Set by syrk.hip's trip_tiles_left; cleared by part_ws, the
+    // one accessor that hands "syrk_part" out to a writer.
     struct {
         int kind = 0, m = 0, n = 0, nranks = 0;
     } lm_trip_tiles;
@@ -370,16 +372,10 @@ int launch_lm_batch(pnol_ctx* ctx, const pnol_lm_batch* b, const double* y, cons
 // residual rows by a fixed tree (syrk.hip), so LevMarqMPI can split the rows over up to
 // kLmSlices ranks with bitwise the one-GPU A.  Sliced J^T layout: slice s is an n x mS
 // row-major block at JTs + s * n * mS (FD column j, rows [s mS, (s + 1) mS) of J).
-constexpr int kLmSlices = 8;
+// (kLmSlices, lm_slice_rows and lm_rank_slices: lm_normal_plan.hpp)
 // columns mode: each rank's last FD tile is launched and exchanged as this many column groups
 // (PNOL_LM_SUBPHASES overrides), so only the last group's m-slices are exposed after the FD
 constexpr int kLmSubphases = 1;
-inline int lm_slice_rows(int m) { return (((m + kLmSlices - 1) / kLmSlices) + 63) / 64 * 64; }
-// rank r of P (<= kLmSlices) holds slices [floor(r 8 / P), floor((r + 1) 8 / P))
-inline void lm_rank_slices(int P, int r, int* s0, int* s1) {
-    *s0 = r * kLmSlices / P;
-    *s1 = (r + 1) * kLmSlices / P;
-}
 // normal equations from the sliced J^T of this rank's slices (all FD columns): A (+ Marquardt
 // diagonal) and rhs = -J^T F on every rank (syrk.hip)
 int launch_lm_normal(pnol_ctx* ctx, const double* JTs, int m, int n, double lambda, const double* F, double* A,

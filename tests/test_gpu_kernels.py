@@ -808,26 +808,54 @@ def test_lm_agree_status_codes_one_rank(ctx):
         assert t.cpu().tolist() == [v, code], (v, t.cpu().tolist())
 
 
-def test_lm_trip_normal_refuses_stale_partials(ctx):
+@pytest.mark.parametrize("writer", ["jtj", "fd_jtj_rows", "fd_normal", "lm_normal_mpi"])
+def test_lm_trip_normal_refuses_stale_partials(ctx, writer):
     """pnol_lm_trip_normal_d forms A only from the partials of the last pnol_lm_trip_d of the same
-    (m, n): after another J^T J call overwrote them, or for another shape, it refuses
-    (PNOL_ERR_ARG) instead of returning a wrong A."""
+    (m, n): after another J^T J call overwrote them -- whichever launcher it went through -- or for
+    another shape, it refuses (PNOL_ERR_ARG) instead of returning a wrong A."""
     from parallelnonlinearoptimizationlibrary_amd import _lib as L
     from parallelnonlinearoptimizationlibrary_amd.device import DeviceObjective
     m, n = 1000, 300
     d = DeviceObjective.synthetic(ctx, L.OBJ_LINRES, n, m)
     x, h = ctx.tensor(np.linspace(-0.5, 0.5, n)), ctx.tensor(np.full(n, 1e-7))
     JT = ctx.empty(n, m)
+    Fs, JTs = d.lm_jacobian_mpi(x, h)                      # (no J^T J in it)
     d.lm_trip(x, h, 0.5, JT)
     ctx.synchronize()
     ctx.lm_trip_normal(m, n, 0.5)                          # the trip's own partials: fine
     with pytest.raises(L.PnolError) as e:
         ctx.lm_trip_normal(m + 64, n, 0.5)                 # another shape
     assert e.value.status == L.PNOL_ERR_ARG
-    ctx.jtj(JT, 0.5)                                       # overwrites the partials
+    if writer == "jtj":                                    # each overwrites the partials
+        ctx.jtj(JT, 0.5)
+    elif writer == "fd_jtj_rows":                          # the row-range form (launch_jtj_rows)
+        d.fd_jtj(x, h, 0.5, JT, ctx.empty(n, n), nchunks=2)
+    elif writer == "fd_normal":
+        d.fd_normal(x, h, 0.5, JT, ctx.empty(n, n), ctx.empty(n))
+    else:                                                  # one rank of LevMarqMPI's normal equations
+        ctx.lm_normal_mpi(JTs, m, n, 0.5, Fs)
     ctx.synchronize()
     with pytest.raises(L.PnolError) as e:
         ctx.lm_trip_normal(m, n, 0.5)
+    assert e.value.status == L.PNOL_ERR_ARG
+
+
+def test_lm_normal_unpack_refuses_stale_partials(ctx):
+    """The mirror case: pnol_lm_normal_unpack_mpi_d forms A only from what the last
+    pnol_lm_normal_solve_mpi_d left; after pnol_jtj_d overwrote the partials it refuses."""
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    from parallelnonlinearoptimizationlibrary_amd.device import DeviceObjective
+    m, n = 1000, 300
+    d = DeviceObjective.synthetic(ctx, L.OBJ_LINRES, n, m)
+    x, h = ctx.tensor(np.linspace(-0.5, 0.5, n)), ctx.tensor(np.full(n, 1e-7))
+    Fs, JTs = d.lm_jacobian_mpi(x, h)
+    ctx.lm_normal_solve_mpi(JTs, m, n, 0.5, Fs, x)
+    ctx.lm_normal_unpack_mpi(m, n, 0.5)                    # the solve's own partials: fine
+    F0, JT = d.fd_jacobian(x, h, 0, n)
+    ctx.jtj(JT, 0.5)
+    ctx.synchronize()
+    with pytest.raises(L.PnolError) as e:
+        ctx.lm_normal_unpack_mpi(m, n, 0.5)
     assert e.value.status == L.PNOL_ERR_ARG
 
 

@@ -35,8 +35,9 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "no device\n");
         return 1;
     }
-    const int nt = (n + kTile - 1) / kTile, ntiles = nt * (nt + 1) / 2;
-    const SliceCfg sc = slice_cfg(m, ntiles);
+    const LmNormalPlan pl = plan_for(m, n);
+    const int nt = pl.nt, ntiles = pl.ntiles;
+    const SliceCfg& sc = pl.sc;
     if (sc.sub != 2) {
         std::fprintf(stderr, "this driver launches the sub = 2 instance\n");
         return 1;

@@ -33,9 +33,9 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "no device\n");
         return 1;
     }
-    const int nt = (n + kTile - 1) / kTile, ntiles = nt * (nt + 1) / 2;
-    const SliceCfg sc = slice_cfg(m, ntiles);
-    const int split = kS * sc.sub, grid = ntiles * split;
+    const LmNormalPlan pl = plan_for(m, n);
+    const SliceCfg& sc = pl.sc;
+    const int ntiles = pl.ntiles, split = pl.split, grid = ntiles * split;
     if (grid > 65536) {
         std::fprintf(stderr, "grid too large for the timeline buffer\n");
         return 1;
@@ -50,7 +50,7 @@ int main(int argc, char** argv) {
     std::vector<float> ms(reps);
     for (int r = 0; r < reps; ++r) {
         hipEventRecord(e0, ctx->stream);
-        syrk_partials(ctx, ctx->stream, false, JT, m, sc.mS, n, m, sc, 0, kS, 0, ntiles, part, false);
+        syrk_partials(ctx, ctx->stream, false, JT, m, sc.mS, pl, 0, kS, 0, ntiles, part, false);
         hipEventRecord(e1, ctx->stream);
         hipEventSynchronize(e1);
         hipEventElapsedTime(&ms[r], e0, e1);
