@@ -54,8 +54,8 @@ int pnol_default_ctx(pnol_ctx** out);
 
 /* Per-kernel HIP-event timers on the context's stream (off by default).  Names: "fd_jacobian",
  * "fd_ckpt", "fd_gradient", "linres_eval", "syrk", "syrk_reduce", "jtr", "solve", "hg",
- * "bfgs_pass", "allgather", "exchange_J", "exchange_A", "lm_batch".  total_ms sums the recorded launches
- * since the last reset.  on = 2 times only "fd_jacobian", "fd_ckpt", "syrk", "exchange_J",
+ * "bfgs_pass", "allgather", "exchange_J", "exchange_A", "lm_batch", "simplex_batch".  total_ms sums the
+ * recorded launches since the last reset.  on = 2 times only "fd_jacobian", "fd_ckpt", "syrk", "exchange_J",
  * "allgather", "hg" and "bfgs_pass" (fewer event records between launches). */
 int pnol_ctx_enable_timers(pnol_ctx* ctx, int on);
 /* (also "exchange_J_busy": the columns-mode exchange's span on its own stream; "exchange_J" is
@@ -373,6 +373,34 @@ int pnol_run_levmarq_batch(int kind, int n, int m, long long nprob, const double
                            const double* ydata, const double* params, double* X, double* chi0, double* chi, int* iters,
                            long long* evals, double* F0, double* FOpt);
 
+/* ---- batched Nelder-Mead: many independent simplex searches in one launch --------------- */
+/* The largest n of a batched search: a lane's simplex, (n + 1)^2 + 3 n doubles, lives in LDS
+ * (64 lanes x 205 doubles = 105 KB at n = 12; the reference's example is n = 10). */
+#define PNOL_SIMPLEX_BATCH_NMAX 12
+/* nstart independent SimplexSearch::findMin runs (SimplexSearch.cpp:13-240) of one scalar device
+ * objective -- PNOL_OBJ_ROSENBROCK, PNOL_OBJ_POWER or PNOL_OBJ_QUADRATIC; other kinds
+ * PNOL_ERR_UNSUPPORTED -- queued on the context stream with no host wait (timer
+ * "simplex_batch"): one GPU lane runs one start's whole search in the reference's operation
+ * order.  params: HOST, 8 doubles in setSimplexParams order (alpha, gamma, rho, sigma, maxIter,
+ * initRandMax, xMinDiff, verbose -- nothing is printed); PNOL_ERR_ARG when maxIter is negative,
+ * NaN or does not fit an int.  X: nstart * n device doubles, the starts in and the optima out;
+ * f0 / fopt: nstart doubles, f at the start and at the optimum; iters: nstart ints, the loop's
+ * iter at exit; evals: nstart long longs, objEval calls the reference would have made.  Start s
+ * draws its initial simplex from the stream seeded seed + s, so it is SimplexSearch with
+ * setSeed(seed + s) from X[s] -- the same bits of X, f0, fOpt, iterations and evaluations,
+ * whatever batch it is in.  (Power with power != 2 calls the device pow and is not bitwise
+ * against the host.)  1 <= n <= PNOL_SIMPLEX_BATCH_NMAX, a larger n PNOL_ERR_UNSUPPORTED;
+ * nstart <= 0 PNOL_ERR_ARG.  The reference has no batched form: this replaces a host loop of
+ * multi-start findMin calls. */
+int pnol_simplex_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* params, unsigned long long seed,
+                               long long nstart, double* X, double* f0, double* fopt, int* iters, long long* evals);
+/* The same with HOST pointers on the process default context: create the objective (kind, n,
+ * power, p0 / p1 as pnol_dobj_create), upload, solve, download, destroy.  Arguments are checked
+ * before any device use; PNOL_ERR_NODEVICE without a gfx950 device. */
+int pnol_run_simplex_batch(int kind, int n, double power, const double* p0, size_t len0, const double* p1,
+                           size_t len1, long long nstart, const double* params, unsigned long long seed, double* X,
+                           double* f0, double* fopt, int* iters, long long* evals);
+
 /* ---- communicator (replaces MPI_COMM_WORLD on the FD / pool paths) ------------------- */
 /* RCCL over xGMI: one process per GPU.  Exchange the 128-byte id out of band (rank 0 creates). */
 int pnol_comm_unique_id(char id[128]);
@@ -463,6 +491,17 @@ int pnol_host_fd_jacobian(pnol_host_multi_fn fn, void* user, const double* x, co
 int pnol_host_run_ga(int which, pnol_host_scalar_fn fn, void* user, const double* params, int nparams,
                      unsigned long long seed, double* X, int n, const double* Xlb, const double* Xub,
                      pnol_result* res);
+/* SimplexSearch::findMin (SimplexSearch.cpp:13-240) on a built-in scalar objective.  params: 8
+ * doubles in setSimplexParams order (alpha, gamma, rho, sigma, maxIter, initRandMax, xMinDiff,
+ * verbose -- nothing is printed); PNOL_ERR_ARG when maxIter is negative, NaN or does not fit an
+ * int.  seed: the initial simplex's stream (SimplexSearch::setSeed); res->iters = the loop's iter
+ * at exit.  The n + 1 vertices of the initial simplex and of a shrink are one device batch for
+ * device objectives (host_eval = 0). */
+int pnol_run_simplex(pnol_dobj* obj, int host_eval, const double* params, unsigned long long seed, double* X, int n,
+                     pnol_result* res);
+/* The same on a C callback objective; needs no device. */
+int pnol_host_run_simplex(pnol_host_scalar_fn fn, void* user, const double* params, unsigned long long seed,
+                          double* X, int n, pnol_result* res);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,7 @@
 #include "GeneticAlgorithmMPI.hpp"
 #include "LevenbergMarquardt.hpp"
 #include "LevenbergMarquardtMPI.hpp"
+#include "SimplexSearch.hpp"
 #include "device_util.hpp"
 #include "scalar_host.hpp"
 #include "../pnol_env.hpp"
@@ -306,6 +307,49 @@ int pnol_host_run_ga(int which, pnol_host_scalar_fn fn, void* user, const double
     return guarded([&] {
         CallbackScalar o(fn, user);
         run_ga_on(o, which, p, seed, X, n, Xlb, Xub, res);
+    });
+}
+
+}  // extern "C"
+
+namespace {
+// SimplexSearch on any Objective; evals: the objective's count.  verbose is never passed on
+template <class Obj>
+void run_simplex_on(Obj& o, const double* p, unsigned long long seed, double* X, int n, pnol_result* res) {
+    std::vector<double> x(X, X + n);
+    double f0 = 0, fopt = 0;
+    SimplexSearch s;
+    s.setSimplexParams(p[0], p[1], p[2], p[3], (int)p[4], p[5], p[6], false);
+    s.setSeed(seed);
+    s.setObjPtr(o);
+    s.findMin(x, f0, fopt);
+    for (int i = 0; i < n; ++i) X[i] = x[i];
+    res->iters = s.getIterations();
+    res->evals = o.evals;
+    res->f0 = f0;
+    res->fopt = fopt;
+}
+}  // namespace
+
+extern "C" {
+
+int pnol_run_simplex(pnol_dobj* obj, int host_eval, const double* p, unsigned long long seed, double* X, int n,
+                     pnol_result* res) {
+    if (!obj || !X || n <= 0 || !res) return PNOL_ERR_ARG;
+    PNOL_CHECK(simplex_check_params(p));
+    return guarded([&] {
+        DriverScalar o(obj, host_eval != 0);
+        run_simplex_on(o, p, seed, X, n, res);
+    });
+}
+
+int pnol_host_run_simplex(pnol_host_scalar_fn fn, void* user, const double* p, unsigned long long seed, double* X,
+                          int n, pnol_result* res) {
+    if (!fn || !X || n <= 0 || !res) return PNOL_ERR_ARG;
+    PNOL_CHECK(simplex_check_params(p));
+    return guarded([&] {
+        CallbackScalar o(fn, user);
+        run_simplex_on(o, p, seed, X, n, res);
     });
 }
 

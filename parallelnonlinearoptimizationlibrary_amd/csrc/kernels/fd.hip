@@ -23,6 +23,7 @@
 #include "../pnol_comm.hpp"
 #include "../pnol_env.hpp"
 #include "multi_residual.hpp"
+#include "scalar_terms.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -156,24 +157,7 @@ __global__ __launch_bounds__(256) void k_eval_batch(const double* __restrict__ X
 // v_add_f64 per term; inside the window each lane forms its own perturbed terms exactly as the
 // objective does.  Same additions in the same order as evaluating each point from scratch
 // (bitwise), one dependent add per term on the critical path instead of the whole term.
-template <int KIND>
-__device__ __forceinline__ int scalar_nterms(int n) { return KIND == PNOL_OBJ_ROSENBROCK ? max(n - 1, 0) : n; }
-
-// term k at the point whose coordinates k, k + 1 are xk, xk1 (the objective's own expression)
-template <int KIND>
-__device__ __forceinline__ double scalar_term(int k, int n, double xk, double xk1, const double* __restrict__ p0,
-                                              const double* __restrict__ p1, double power) {
-    if (KIND == PNOL_OBJ_ROSENBROCK) {
-        const double t = xk1 - xk * xk, u = 1.0 - xk;   // ExampleObjectives.hpp:93-96
-        return 100.0 * (t * t) + u * u;
-    } else if (KIND == PNOL_OBJ_QUADRATIC) {
-        double t = (0.5 * p0[k] * xk) * xk - p1[k] * xk;
-        if (k + 1 < n) t = t + (0.25 * xk) * xk1;
-        return t;
-    } else {
-        return power == 2.0 ? xk * xk : pow(xk, power);
-    }
-}
+// (scalar_nterms / scalar_term: scalar_terms.hpp)
 
 // xcopy (the host-pointer gradient): x is the caller's pinned host block, read once here over
 // PCIe and copied to device memory for the chain kernel -- no separate host-to-device copy;

@@ -367,6 +367,18 @@ int launch_fill(pnol_ctx* ctx, double* p, size_t count, double value);
 // params: host, LevMarq::setParams order; X: x0 in, optimum out; F0 / FOpt nullable
 int launch_lm_batch(pnol_ctx* ctx, const pnol_lm_batch* b, const double* y, const double* params, double* X,
                     double* chi0, double* chi, int* iters, long long* evals, double* F0, double* FOpt);
+// nstart independent SimplexSearch::findMin runs of one scalar objective in one launch, one lane
+// per start (simplex_batch.hip).  params: host, setSimplexParams order (maxIter already checked);
+// start s draws from the stream seeded seed + s; X: the starts in, the optima out
+// the 8 setSimplexParams values of the C ABI: maxIter (a double there, cast to int) must be a
+// non-negative int; nothing here touches a device
+inline int simplex_check_params(const double* p) {
+    if (!p) return PNOL_ERR_ARG;
+    if (!(p[4] >= 0.0 && p[4] <= 2147483647.0)) return PNOL_ERR_ARG;
+    return PNOL_OK;
+}
+int launch_simplex_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, unsigned long long seed,
+                         long long nstart, double* X, double* f0, double* fopt, int* iters, long long* evals);
 
 // ---- LM m-slices: J^T J and J^T F are summed over kLmSlices slices of the m
 // residual rows by a fixed tree (syrk.hip), so LevMarqMPI can split the rows over up to

@@ -461,6 +461,78 @@ def run_ga(obj: DeviceObjective, x0, lb, ub, params, seed, which=0, host_eval=Fa
     return X, res
 
 
+SIMPLEX_DEFAULTS = (1.0, 2.0, 0.5, 0.5, 10000, 1.0, 1e-7, 0)   # SimplexSearch's constructor
+
+
+def _simplex_params(params):
+    p = np.array(params, dtype=np.float64)
+    if p.size != 8:
+        raise ValueError("params: the 8 values of SimplexSearch::setSimplexParams")
+    return p
+
+
+def run_simplex(obj: DeviceObjective, x0, params, seed, host_eval=False):
+    """Run the C++ drop-in SimplexSearch on a scalar device objective with a fixed initial-simplex
+    stream; params = setSimplexParams (8 values).  Returns (X, result); result.iters = trips."""
+    X = np.array(x0, dtype=np.float64)
+    p = _simplex_params(params)
+    res = L.Result()
+    L.check(L.lib().pnol_run_simplex(obj.h, int(host_eval), _dptr(p), seed, _dptr(X), X.size, C.byref(res)),
+            "pnol_run_simplex")
+    return X, res
+
+
+def host_run_simplex(fn, x0, params, seed):
+    """SimplexSearch on a Python objective fn(x: numpy array) -> float, through the C callback
+    entry point (no device).  Returns (X, result)."""
+    X = np.array(x0, dtype=np.float64)
+    p = _simplex_params(params)
+    res = L.Result()
+    cb = L.HOST_SCALAR_FN(lambda xp, n, _user: float(fn(np.ctypeslib.as_array(xp, shape=(n,)).copy())))
+    L.check(L.lib().pnol_host_run_simplex(cb, None, _dptr(p), seed, _dptr(X), X.size, C.byref(res)),
+            "pnol_host_run_simplex")
+    return X, res
+
+
+def run_simplex_batch(obj, x0, params, seed, kind=None, power=2.0, p0=None, p1=None):
+    """Batched SimplexSearch: the nstart rows of x0 (nstart x n) are independent searches of one
+    scalar objective in one launch, start s on the stream seeded seed + s; params =
+    setSimplexParams (8 values).  obj: a DeviceObjective (solved on its context through
+    pnol_simplex_batch_solve_d), or None for the process default context through the host-pointer
+    entry point pnol_run_simplex_batch, the objective then given by kind / power / p0 / p1.
+    Returns (X, f0, fopt, iters, evals) as numpy arrays."""
+    X = np.ascontiguousarray(np.array(x0, dtype=np.float64))
+    if X.ndim != 2:
+        raise ValueError("x0 must be nstart x n")
+    nstart, n = int(X.shape[0]), int(X.shape[1])
+    p = _simplex_params(params)
+    if obj is not None:
+        if n != obj.n:
+            raise ValueError("x0 rows must have the objective's n values")
+        ctx = obj.ctx
+        t = ctx.torch
+        dev = f"cuda:{ctx.device}"
+        Xd = ctx.tensor(X)
+        f0, fo = ctx.empty(max(nstart, 1)), ctx.empty(max(nstart, 1))
+        iters = t.empty(max(nstart, 1), dtype=t.int32, device=dev)
+        evals = t.empty(max(nstart, 1), dtype=t.int64, device=dev)
+        L.check(L.lib().pnol_simplex_batch_solve_d(ctx.h, obj.h, _dptr(p), seed, nstart, _ptr(Xd), _ptr(f0), _ptr(fo),
+                                                   _ptr(iters), _ptr(evals)), "pnol_simplex_batch_solve_d")
+        ctx.synchronize()
+        return tuple(a.cpu().numpy() for a in (Xd, f0, fo, iters, evals))
+    a0 = None if p0 is None else np.ascontiguousarray(p0, dtype=np.float64).ravel()
+    a1 = None if p1 is None else np.ascontiguousarray(p1, dtype=np.float64).ravel()
+    f0, fo = np.zeros(max(nstart, 1)), np.zeros(max(nstart, 1))
+    iters, evals = np.zeros(max(nstart, 1), dtype=np.int32), np.zeros(max(nstart, 1), dtype=np.int64)
+    Xh = X if X.size else np.zeros(1)
+    L.check(L.lib().pnol_run_simplex_batch(kind, n, C.c_double(power), _dptr(a0) if a0 is not None else None,
+                                           0 if a0 is None else a0.size, _dptr(a1) if a1 is not None else None,
+                                           0 if a1 is None else a1.size, nstart, _dptr(p), seed, _dptr(Xh), _dptr(f0),
+                                           _dptr(fo), iters.ctypes.data_as(C.POINTER(C.c_int)),
+                                           evals.ctypes.data_as(C.POINTER(C.c_longlong))), "pnol_run_simplex_batch")
+    return X, f0[:nstart], fo[:nstart], iters[:nstart], evals[:nstart]
+
+
 def run_levmarq(obj: DeviceObjective, x0, params, which=0, host_eval=False):
     """Run the C++ drop-in LevMarq (0) or LevMarqMPI (1); returns (X, F0, FOpt, result)."""
     X = np.array(x0, dtype=np.float64)
