@@ -54,9 +54,10 @@ int pnol_default_ctx(pnol_ctx** out);
 
 /* Per-kernel HIP-event timers on the context's stream (off by default).  Names: "fd_jacobian",
  * "fd_ckpt", "fd_gradient", "linres_eval", "syrk", "syrk_reduce", "jtr", "solve", "hg",
- * "bfgs_pass", "allgather", "exchange_J", "exchange_A", "lm_batch", "simplex_batch".  total_ms sums the
- * recorded launches since the last reset.  on = 2 times only "fd_jacobian", "fd_ckpt", "syrk", "exchange_J",
- * "allgather", "hg" and "bfgs_pass" (fewer event records between launches). */
+ * "bfgs_pass", "allgather", "exchange_J", "exchange_A", "lm_batch", "simplex_batch",
+ * "bfgs_batch".  total_ms sums the recorded launches since the last reset.  on = 2 times only
+ * "fd_jacobian", "fd_ckpt", "syrk", "exchange_J", "allgather", "hg" and "bfgs_pass" (fewer event
+ * records between launches). */
 int pnol_ctx_enable_timers(pnol_ctx* ctx, int on);
 /* (also "exchange_J_busy": the columns-mode exchange's span on its own stream; "exchange_J" is
  * then the part of it left after the FD launches end -- the exposed exchange) */
@@ -400,6 +401,38 @@ int pnol_simplex_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* para
 int pnol_run_simplex_batch(int kind, int n, double power, const double* p0, size_t len0, const double* p1,
                            size_t len1, long long nstart, const double* params, unsigned long long seed, double* X,
                            double* f0, double* fopt, int* iters, long long* evals);
+
+/* ---- batched BFGS: many independent Wolfe-line-search solves in one launch -------------- */
+/* The largest n of a batched solve: a lane's D and vectors, n^2 + 6 n doubles, live in LDS
+ * (64 lanes x 216 doubles = 108 KB at n = 12). */
+#define PNOL_BFGS_BATCH_NMAX 12
+/* nstart independent BFGS::findMin runs (BFGS_with_linesearch.cpp:12-432) of one scalar device
+ * objective -- PNOL_OBJ_ROSENBROCK, PNOL_OBJ_POWER or PNOL_OBJ_QUADRATIC; other kinds
+ * PNOL_ERR_UNSUPPORTED -- queued on the context stream with no host wait (timer "bfgs_batch"):
+ * one GPU lane runs one start's whole solve (FD gradient, cubic-interpolation Wolfe line search
+ * with its zoom, the exact update D <- M1 D M2 + M3) in the reference's operation order.
+ * params: HOST, 12 doubles in BFGS::setParams order (c1, c2, dalpha, alphaGuess,
+ * maxIterLineSearch, dXGrad, dXHess, maxIter, xMinDiff, minGrad2Norm, initHessFD, verbose);
+ * dXHess and verbose are accepted and ignored (nothing is printed), initHessFD != 0 is
+ * PNOL_ERR_UNSUPPORTED (D starts as the identity), PNOL_ERR_ARG when maxIter or
+ * maxIterLineSearch is negative, NaN or does not fit an int.  X: nstart * n device doubles, the
+ * starts in and the optima out; f0 / fopt: nstart doubles, f at the start and at the optimum;
+ * gnorm: nstart doubles, the loop's last gradient 2-norm (2 * minGrad2Norm when no trip ran),
+ * which tells a converged start from one that ended through an exhausted line search; iters:
+ * nstart ints, the loop's iter at exit; evals: nstart long longs, objEval calls the reference
+ * would have made from the first gradient on.  Start s is BFGS::findMin from X[s] -- the same bits
+ * of X, f0, fOpt, iterations and evaluations, whatever batch it is in.  (Power with power != 2
+ * calls the device pow and is not bitwise against the host.)  1 <= n <= PNOL_BFGS_BATCH_NMAX, a
+ * larger n PNOL_ERR_UNSUPPORTED; nstart <= 0 PNOL_ERR_ARG.  The reference has no batched form:
+ * this replaces a host loop of multi-start findMin calls. */
+int pnol_bfgs_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* params, long long nstart, double* X,
+                            double* f0, double* fopt, double* gnorm, int* iters, long long* evals);
+/* The same with HOST pointers on the process default context: create the objective (kind, n,
+ * power, p0 / p1 as pnol_dobj_create), upload, solve, download, destroy.  Arguments are checked
+ * before any device use; PNOL_ERR_NODEVICE without a gfx950 device. */
+int pnol_run_bfgs_batch(int kind, int n, double power, const double* p0, size_t len0, const double* p1, size_t len1,
+                        long long nstart, const double* params, double* X, double* f0, double* fopt, double* gnorm,
+                        int* iters, long long* evals);
 
 /* ---- communicator (replaces MPI_COMM_WORLD on the FD / pool paths) ------------------- */
 /* RCCL over xGMI: one process per GPU.  Exchange the 128-byte id out of band (rank 0 creates). */

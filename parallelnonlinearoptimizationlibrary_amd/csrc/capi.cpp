@@ -775,3 +775,74 @@ int pnol_run_simplex_batch(int kind, int n, double power, const double* p0, size
 }
 
 }  // extern "C"
+
+// ---- batched BFGS (bfgs_batch.hip) ---------------------------------------------------------
+namespace {
+
+// kind / size checks shared by the device- and the host-pointer call; nothing here touches a device
+int bfb_check_shape(int kind, int n, long long nstart) {
+    if (kind != PNOL_OBJ_ROSENBROCK && kind != PNOL_OBJ_POWER && kind != PNOL_OBJ_QUADRATIC)
+        return PNOL_ERR_UNSUPPORTED;
+    if (n <= 0 || nstart <= 0) return PNOL_ERR_ARG;
+    if (n > PNOL_BFGS_BATCH_NMAX) return PNOL_ERR_UNSUPPORTED;
+    return PNOL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pnol_bfgs_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* params, long long nstart, double* X,
+                            double* f0, double* fopt, double* gnorm, int* iters, long long* evals) {
+    if (!ctx || !obj) return PNOL_ERR_ARG;
+    PNOL_CHECK(bfgs_batch_check_params(params));
+    PNOL_CHECK(bfb_check_shape(obj->kind, obj->n, nstart));
+    if (!X || !f0 || !fopt || !gnorm || !iters || !evals || obj->device != ctx->device) return PNOL_ERR_ARG;
+    PNOL_CHECK(set_device(ctx));
+    return launch_bfgs_batch(ctx, obj, params, nstart, X, f0, fopt, gnorm, iters, evals);
+}
+
+int pnol_run_bfgs_batch(int kind, int n, double power, const double* p0, size_t len0, const double* p1, size_t len1,
+                        long long nstart, const double* params, double* X, double* f0, double* fopt, double* gnorm,
+                        int* iters, long long* evals) {
+    PNOL_CHECK(bfgs_batch_check_params(params));
+    PNOL_CHECK(bfb_check_shape(kind, n, nstart));
+    if (kind == PNOL_OBJ_QUADRATIC && (!p0 || !p1 || len0 < (size_t)n || len1 < (size_t)n)) return PNOL_ERR_ARG;
+    if (!X || !f0 || !fopt || !gnorm || !iters || !evals) return PNOL_ERR_ARG;
+    pnol_ctx* ctx = nullptr;
+    PNOL_CHECK(pnol_default_ctx(&ctx));
+    PNOL_CHECK(set_device(ctx));
+    pnol_dobj* o = nullptr;
+    PNOL_CHECK(pnol_dobj_create(ctx, kind, n, 0, p0, len0, p1, len1, power, &o));
+    const size_t ns = (size_t)nstart;
+    // one device block: X | f0 | fopt | gnorm | evals | iters (8-byte items first)
+    const size_t bytes = sizeof(double) * (ns * n + 3 * ns) + sizeof(long long) * ns + sizeof(int) * ns;
+    char* dv = nullptr;
+    int st = hipMalloc(&dv, bytes) == hipSuccess ? PNOL_OK : PNOL_ERR_NOMEM;
+    auto hip = [&](hipError_t e) {
+        if (st == PNOL_OK && e != hipSuccess) st = PNOL_ERR_HIP;
+    };
+    if (st == PNOL_OK) {
+        double* dX = (double*)dv;
+        double* df0 = dX + ns * n;
+        double* dfo = df0 + ns;
+        double* dgn = dfo + ns;
+        long long* dev = (long long*)(dgn + ns);
+        int* dit = (int*)(dev + ns);
+        hip(hipMemcpyAsync(dX, X, sizeof(double) * ns * n, hipMemcpyHostToDevice, ctx->stream));
+        if (st == PNOL_OK) st = launch_bfgs_batch(ctx, o, params, nstart, dX, df0, dfo, dgn, dit, dev);
+        hip(hipMemcpyAsync(X, dX, sizeof(double) * ns * n, hipMemcpyDeviceToHost, ctx->stream));
+        hip(hipMemcpyAsync(f0, df0, sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
+        hip(hipMemcpyAsync(fopt, dfo, sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
+        hip(hipMemcpyAsync(gnorm, dgn, sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
+        hip(hipMemcpyAsync(evals, dev, sizeof(long long) * ns, hipMemcpyDeviceToHost, ctx->stream));
+        hip(hipMemcpyAsync(iters, dit, sizeof(int) * ns, hipMemcpyDeviceToHost, ctx->stream));
+        if (const int w = stream_wait(ctx->stream))
+            if (st == PNOL_OK) st = w;
+    }
+    if (dv) (void)hipFree(dv);
+    pnol_dobj_destroy(o);
+    return st;
+}
+
+}  // extern "C"

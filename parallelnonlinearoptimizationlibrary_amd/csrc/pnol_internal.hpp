@@ -379,6 +379,20 @@ inline int simplex_check_params(const double* p) {
 }
 int launch_simplex_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, unsigned long long seed,
                          long long nstart, double* X, double* f0, double* fopt, int* iters, long long* evals);
+// the 12 BFGS::setParams values of the batched C ABI: maxIterLineSearch and maxIter (doubles
+// there, cast to int) must be non-negative ints, and the FD initial Hessian is not offered;
+// nothing here touches a device
+inline int bfgs_batch_check_params(const double* p) {
+    if (!p) return PNOL_ERR_ARG;
+    if (!(p[4] >= 0.0 && p[4] <= 2147483647.0) || !(p[7] >= 0.0 && p[7] <= 2147483647.0)) return PNOL_ERR_ARG;
+    if (p[10] != 0.0) return PNOL_ERR_UNSUPPORTED;
+    return PNOL_OK;
+}
+// nstart independent BFGS::findMin runs of one scalar objective in one launch, one lane per start
+// (bfgs_batch.hip).  params: host, BFGS::setParams order (already checked); X: the starts in, the
+// optima out
+int launch_bfgs_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, long long nstart, double* X,
+                      double* f0, double* fopt, double* gnorm, int* iters, long long* evals);
 
 // ---- LM m-slices: J^T J and J^T F are summed over kLmSlices slices of the m
 // residual rows by a fixed tree (syrk.hip), so LevMarqMPI can split the rows over up to

@@ -533,6 +533,47 @@ def run_simplex_batch(obj, x0, params, seed, kind=None, power=2.0, p0=None, p1=N
     return X, f0[:nstart], fo[:nstart], iters[:nstart], evals[:nstart]
 
 
+def run_bfgs_batch(obj, x0, params, kind=None, power=2.0, p0=None, p1=None):
+    """Batched BFGS: the nstart rows of x0 (nstart x n) are independent BFGS::findMin runs of one
+    scalar objective in one launch; params = BFGS::setParams (12 values; initHessFD must be 0).
+    obj: a DeviceObjective (solved on its context through pnol_bfgs_batch_solve_d), or None for
+    the process default context through the host-pointer entry point pnol_run_bfgs_batch, the
+    objective then given by kind / power / p0 / p1.  Returns (X, f0, fopt, gnorm, iters, evals) as
+    numpy arrays; gnorm is the loop's last gradient norm."""
+    X = np.ascontiguousarray(np.array(x0, dtype=np.float64))
+    if X.ndim != 2:
+        raise ValueError("x0 must be nstart x n")
+    nstart, n = int(X.shape[0]), int(X.shape[1])
+    p = np.array(params, dtype=np.float64)
+    if p.size != 12:
+        raise ValueError("params: the 12 values of BFGS::setParams")
+    if obj is not None:
+        if n != obj.n:
+            raise ValueError("x0 rows must have the objective's n values")
+        ctx = obj.ctx
+        t = ctx.torch
+        dev = f"cuda:{ctx.device}"
+        Xd = ctx.tensor(X)
+        f0, fo, gn = ctx.empty(max(nstart, 1)), ctx.empty(max(nstart, 1)), ctx.empty(max(nstart, 1))
+        iters = t.empty(max(nstart, 1), dtype=t.int32, device=dev)
+        evals = t.empty(max(nstart, 1), dtype=t.int64, device=dev)
+        L.check(L.lib().pnol_bfgs_batch_solve_d(ctx.h, obj.h, _dptr(p), nstart, _ptr(Xd), _ptr(f0), _ptr(fo), _ptr(gn),
+                                                _ptr(iters), _ptr(evals)), "pnol_bfgs_batch_solve_d")
+        ctx.synchronize()
+        return tuple(a.cpu().numpy() for a in (Xd, f0, fo, gn, iters, evals))
+    a0 = None if p0 is None else np.ascontiguousarray(p0, dtype=np.float64).ravel()
+    a1 = None if p1 is None else np.ascontiguousarray(p1, dtype=np.float64).ravel()
+    f0, fo, gn = np.zeros(max(nstart, 1)), np.zeros(max(nstart, 1)), np.zeros(max(nstart, 1))
+    iters, evals = np.zeros(max(nstart, 1), dtype=np.int32), np.zeros(max(nstart, 1), dtype=np.int64)
+    Xh = X if X.size else np.zeros(1)
+    L.check(L.lib().pnol_run_bfgs_batch(kind, n, C.c_double(power), _dptr(a0) if a0 is not None else None,
+                                        0 if a0 is None else a0.size, _dptr(a1) if a1 is not None else None,
+                                        0 if a1 is None else a1.size, nstart, _dptr(p), _dptr(Xh), _dptr(f0),
+                                        _dptr(fo), _dptr(gn), iters.ctypes.data_as(C.POINTER(C.c_int)),
+                                        evals.ctypes.data_as(C.POINTER(C.c_longlong))), "pnol_run_bfgs_batch")
+    return X, f0[:nstart], fo[:nstart], gn[:nstart], iters[:nstart], evals[:nstart]
+
+
 def run_levmarq(obj: DeviceObjective, x0, params, which=0, host_eval=False):
     """Run the C++ drop-in LevMarq (0) or LevMarqMPI (1); returns (X, F0, FOpt, result)."""
     X = np.array(x0, dtype=np.float64)

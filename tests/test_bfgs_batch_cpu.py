@@ -1,0 +1,161 @@
+"""Batched BFGS, the parts that need no GPU: the plain-Python restatement of BFGS::findMin
+(tests/bfgs_reference.py) against the oracle bit for bit, proof that the standard batches take
+every branch of the line search, the argument checks of the two entry points (all made before any
+device use), and the C++11 compile check of the header."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import bfgs_reference as BR
+from conftest import ROOT
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).tobytes()
+
+
+CASES = [("rosenbrock", 3, 130, BR.DEFAULTS), ("rosenbrock", 2, 65, BR.DEFAULTS), ("rosenbrock", 5, 65, BR.DEFAULTS),
+         ("rosenbrock", 12, 65, BR.DEFAULTS), ("power2", 1, 65, BR.DEFAULTS), ("quadratic", 5, 65, BR.DEFAULTS),
+         ("rosenbrock", 3, 65, BR.params(maxIterLineSearch=2)), ("rosenbrock", 3, 65, BR.params(maxIter=0))]
+IDS = ["rosenbrock-n3", "rosenbrock-n2", "rosenbrock-n5", "rosenbrock-n12", "power2-n1", "quadratic-n5",
+       "maxIterLineSearch2", "maxIter0"]
+
+
+@pytest.mark.parametrize("name,n,nstart,p", CASES, ids=IDS)
+def test_restatement_bitwise_against_oracle(oracle, name, n, nstart, p):
+    """X, f0, fOpt, iterations and evaluations of every start are oracle.bfgs_findmin's."""
+    runs = BR.standard_batch(oracle, name, n, nstart, p)
+    obj = BR.oracle_obj(oracle, name, n)
+    x0 = BR.standard_x0(nstart, n)
+    for s in range(nstart):
+        X, res, _ = oracle.bfgs_findmin(obj, x0[s], p)
+        r = runs[s]
+        assert _bits(X) == _bits(r.X), s
+        assert _bits(np.float64(res.f0)) == _bits(np.float64(r.f0)), s
+        assert _bits(np.float64(res.fopt)) == _bits(np.float64(r.fopt)), s
+        assert (res.iters, res.evals) == (r.iters, r.evals), s
+
+
+def test_standard_batch_takes_every_branch(oracle):
+    """Guards the inputs of the bitwise tests: over the 130 Rosenbrock n = 3 starts neighbouring
+    lanes leave the loop at different trips and every branch of the line search is taken -- the
+    zero bracket width, the NaN steps and the exhausted zoom among them -- except the exhausted
+    outer search, which has an input of its own."""
+    runs = BR.standard_batch(oracle, "rosenbrock", 3, 130)
+    assert len(set(r.iters for r in runs)) >= 3
+    total = dict(zip(BR.COUNTERS, np.sum([r.counts for r in runs], axis=0).tolist()))
+    assert all(v > 0 for k, v in total.items() if k != "outer_exhausted"), total
+
+
+def test_outer_search_exhausted_input(oracle):
+    name, n, x0, p = BR.OUTER_EXHAUSTED
+    obj = BR.oracle_obj(oracle, name, n)
+    r = BR.find_min(BR.oracle_fn(oracle, obj), np.array(x0), p)
+    counts = dict(zip(BR.COUNTERS, r.counts))
+    assert counts["outer_exhausted"] >= 1 and counts["step_doubled"] >= 3, counts
+    X, res, _ = oracle.bfgs_findmin(obj, np.array(x0), p)
+    assert _bits(X) == _bits(r.X) and (res.iters, res.evals) == (r.iters, r.evals)
+    assert res.fopt == r.fopt == r.f0 and r.X[0] == 3.0   # alphaOpt = 0: the start is kept
+
+
+def test_stacked_has_the_library_dtypes(oracle):
+    X, f0, fopt, gnorm, iters, evals = BR.stacked(BR.standard_batch(oracle, "power2", 1, 65))
+    assert X.shape == (65, 1) and X.dtype == f0.dtype == fopt.dtype == gnorm.dtype == np.float64
+    assert iters.dtype == np.int32 and evals.dtype == np.int64
+
+
+# ---- argument checks: before any device use, so the same with or without a GPU ------------
+def _batch(kind, n, nstart, params=BR.DEFAULTS, len0=None, len1=None, null=None):
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    ns, nn = max(nstart, 1), max(n, 1)
+    X = np.full(ns * nn, 3.0)
+    f0, fo, gn = np.zeros(ns), np.zeros(ns), np.zeros(ns)
+    iters, evals = np.zeros(ns, dtype=np.int32), np.zeros(ns, dtype=np.int64)
+    p = np.array(params, dtype=np.float64)
+    d = np.ones(nn)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    args = {"p": dp(p), "X": dp(X), "f0": dp(f0), "fopt": dp(fo), "gnorm": dp(gn),
+            "iters": iters.ctypes.data_as(C.POINTER(C.c_int)), "evals": evals.ctypes.data_as(C.POINTER(C.c_longlong))}
+    if null:
+        args[null] = None
+    return L.lib().pnol_run_bfgs_batch(kind, n, 2.0, dp(d), d.size if len0 is None else len0, dp(d),
+                                       d.size if len1 is None else len1, nstart, args["p"], args["X"], args["f0"],
+                                       args["fopt"], args["gnorm"], args["iters"], args["evals"])
+
+
+def test_entry_points_exist():
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    for name in ("pnol_bfgs_batch_solve_d", "pnol_run_bfgs_batch"):
+        assert hasattr(L.lib(), name), name
+        assert name in L.declared_symbols()
+    hdr = open(os.path.join(ROOT, "include", "pnol_amd.h")).read()
+    assert "#define PNOL_BFGS_BATCH_NMAX 12" in hdr
+    assert L.BFGS_BATCH_NMAX == 12
+    assert '"bfgs_batch"' in hdr   # the timer list names it
+
+
+def test_init_hess_fd_is_unsupported():
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    assert _batch(L.OBJ_ROSENBROCK, 3, 8, BR.params(initHessFD=1)) == L.PNOL_ERR_UNSUPPORTED
+
+
+def test_other_kinds_are_unsupported():
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    assert _batch(L.OBJ_LINRES, 3, 8) == L.PNOL_ERR_UNSUPPORTED
+    assert _batch(L.OBJ_CUBIC, 4, 8) == L.PNOL_ERR_UNSUPPORTED
+    assert _batch(L.OBJ_EXPCURVE, 3, 8) == L.PNOL_ERR_UNSUPPORTED
+
+
+def test_n_above_nmax_is_unsupported():
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    assert _batch(L.OBJ_ROSENBROCK, L.BFGS_BATCH_NMAX + 1, 8) == L.PNOL_ERR_UNSUPPORTED
+    assert _batch(L.OBJ_ROSENBROCK, 16, 8) == L.PNOL_ERR_UNSUPPORTED
+
+
+@pytest.mark.parametrize("which", ["maxIter", "maxIterLineSearch"])
+@pytest.mark.parametrize("value", [-1, float("nan"), float("inf"), 2.0 ** 31])
+def test_bad_iteration_caps_are_refused(which, value):
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    assert _batch(L.OBJ_ROSENBROCK, 3, 8, BR.params(**{which: value})) == L.PNOL_ERR_ARG
+
+
+def test_bad_sizes_and_null_pointers_are_refused():
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    assert _batch(L.OBJ_ROSENBROCK, 3, 0) == L.PNOL_ERR_ARG
+    assert _batch(L.OBJ_ROSENBROCK, 3, -5) == L.PNOL_ERR_ARG
+    assert _batch(L.OBJ_ROSENBROCK, 0, 8) == L.PNOL_ERR_ARG
+    assert _batch(L.OBJ_ROSENBROCK, -2, 8) == L.PNOL_ERR_ARG
+    for null in ("p", "X", "f0", "fopt", "gnorm", "iters", "evals"):
+        assert _batch(L.OBJ_ROSENBROCK, 3, 8, null=null) == L.PNOL_ERR_ARG, null
+    # the device-pointer entry point without a context or an objective
+    assert L.lib().pnol_bfgs_batch_solve_d(None, None, None, 8, None, None, None, None, None, None) == L.PNOL_ERR_ARG
+
+
+def test_short_quadratic_data_is_refused():
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    assert _batch(L.OBJ_QUADRATIC, 5, 8, len0=4) == L.PNOL_ERR_ARG
+    assert _batch(L.OBJ_QUADRATIC, 5, 8, len1=4) == L.PNOL_ERR_ARG
+
+
+def test_no_device_is_reported_on_a_cpu_host():
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    if L.device_count() > 0:
+        pytest.skip("a GPU is visible")
+    assert _batch(L.OBJ_ROSENBROCK, 3, 8) == L.PNOL_ERR_NODEVICE
+    assert _batch(L.OBJ_QUADRATIC, 12, 1) == L.PNOL_ERR_NODEVICE
+    # dXHess and verbose are accepted and ignored: the call gets as far as the device
+    assert _batch(L.OBJ_ROSENBROCK, 3, 8, BR.params(dXHess=float("nan"), verbose=1)) == L.PNOL_ERR_NODEVICE
+    from parallelnonlinearoptimizationlibrary_amd.device import run_bfgs_batch
+    with pytest.raises(L.PnolError) as e:
+        run_bfgs_batch(None, BR.standard_x0(8, 3), BR.DEFAULTS, kind=L.OBJ_ROSENBROCK)
+    assert e.value.status == L.PNOL_ERR_NODEVICE
+
+
+def test_header_compiles_as_cxx11(tmp_path):
+    """include/BFGS_with_linesearch_Batch.hpp in a C++11 program, warnings as errors (compile only)."""
+    src = os.path.join(ROOT, "tests", "cpp", "bfgs_batch_cxx.cpp")
+    subprocess.run(["g++", "-std=c++0x", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", src,
+                    "-o", str(tmp_path / "bfgs_batch_cxx.o")], check=True)
