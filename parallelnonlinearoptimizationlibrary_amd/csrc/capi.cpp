@@ -6,6 +6,7 @@
 
 #include <algorithm>
 
+#include "host_block.hpp"
 #include "pnol_comm.hpp"
 #include "pnol_internal.hpp"
 
@@ -586,6 +587,49 @@ int pnol_fd_jacobian_tiles_d(pnol_ctx* ctx, pnol_dobj* obj, const double* x, con
 
 }  // extern "C"
 
+// ---- the host-pointer driver of the batched solvers (pnol_run_*_batch) ----------------------
+namespace {
+
+// The arrays in one device block (host_block.hpp), the copies in, launch(d) with d[i] the device
+// pointer of array i (null for one left out), the copies out in list order, one wait.  The block
+// is freed on every path; PNOL_ERR_NOMEM when it cannot be had, else the first failing status.
+template <size_t N, typename Launch>
+int run_host_block(pnol_ctx* ctx, const HostArray (&a)[N], Launch&& launch) {
+    size_t off[N];
+    const size_t bytes = host_block_carve(a, N, off);
+    char* dv = nullptr;
+    if (hipMalloc(&dv, bytes) != hipSuccess) return PNOL_ERR_NOMEM;
+    int st = PNOL_OK;
+    auto hip = [&](hipError_t e) {
+        if (st == PNOL_OK && e != hipSuccess) st = PNOL_ERR_HIP;
+    };
+    void* d[N];
+    for (size_t i = 0; i < N; ++i) d[i] = a[i].host ? dv + off[i] : nullptr;
+    for (size_t i = 0; i < N; ++i)
+        if (a[i].host && (a[i].dir & kHostIn))
+            hip(hipMemcpyAsync(d[i], a[i].host, a[i].bytes(), hipMemcpyHostToDevice, ctx->stream));
+    if (st == PNOL_OK) st = launch(d);
+    for (size_t i = 0; i < N; ++i)
+        if (a[i].host && (a[i].dir & kHostOut))
+            hip(hipMemcpyAsync(a[i].host, d[i], a[i].bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    if (const int w = stream_wait(ctx->stream))
+        if (st == PNOL_OK) st = w;
+    (void)hipFree(dv);
+    return st;
+}
+
+// kind / size checks of the two scalar-objective batches (nmax: the solver's PNOL_*_BATCH_NMAX),
+// shared by the device- and the host-pointer call; nothing here touches a device
+int scalar_batch_check_shape(int kind, int n, long long nstart, int nmax) {
+    if (kind != PNOL_OBJ_ROSENBROCK && kind != PNOL_OBJ_POWER && kind != PNOL_OBJ_QUADRATIC)
+        return PNOL_ERR_UNSUPPORTED;
+    if (n <= 0 || nstart <= 0) return PNOL_ERR_ARG;
+    if (n > nmax) return PNOL_ERR_UNSUPPORTED;
+    return PNOL_OK;
+}
+
+}  // namespace
+
 // ---- batched Levenberg-Marquardt (lm_batch.hip) -------------------------------------------
 namespace {
 
@@ -669,65 +713,25 @@ int pnol_run_levmarq_batch(int kind, int n, int m, long long nprob, const double
     pnol_lm_batch* b = nullptr;
     PNOL_CHECK(pnol_lm_batch_create(ctx, kind, n, m, nprob, xdata, xlen, &b));
     const size_t np = (size_t)nprob, nm = np * (size_t)m;
-    // one device block: y | X | chi0 | chi | evals | iters | F0 | FOpt (8-byte items first)
-    const size_t nF = (F0 ? nm : 0) + (FOpt ? nm : 0);
-    const size_t bytes = sizeof(double) * (nm + np * n + 2 * np + nF) + sizeof(long long) * np + sizeof(int) * np;
-    char* dv = nullptr;
-    int st = hipMalloc(&dv, bytes) == hipSuccess ? PNOL_OK : PNOL_ERR_NOMEM;
-    auto hip = [&](hipError_t e) {
-        if (st == PNOL_OK && e != hipSuccess) st = PNOL_ERR_HIP;
-    };
-    if (st == PNOL_OK) {
-        double* dy = (double*)dv;
-        double* dX = dy + nm;
-        double* dc0 = dX + np * n;
-        double* dc = dc0 + np;
-        long long* dev = (long long*)(dc + np);
-        double* dF0 = (double*)(dev + np);
-        double* dFO = dF0 + (F0 ? nm : 0);
-        int* dit = (int*)(dFO + (FOpt ? nm : 0));
-        hip(hipMemcpyAsync(dy, ydata, sizeof(double) * nm, hipMemcpyHostToDevice, ctx->stream));
-        hip(hipMemcpyAsync(dX, X, sizeof(double) * np * n, hipMemcpyHostToDevice, ctx->stream));
-        if (st == PNOL_OK)
-            st = launch_lm_batch(ctx, b, dy, params, dX, dc0, dc, dit, dev, F0 ? dF0 : nullptr, FOpt ? dFO : nullptr);
-        hip(hipMemcpyAsync(X, dX, sizeof(double) * np * n, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(chi0, dc0, sizeof(double) * np, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(chi, dc, sizeof(double) * np, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(evals, dev, sizeof(long long) * np, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(iters, dit, sizeof(int) * np, hipMemcpyDeviceToHost, ctx->stream));
-        if (F0) hip(hipMemcpyAsync(F0, dF0, sizeof(double) * nm, hipMemcpyDeviceToHost, ctx->stream));
-        if (FOpt) hip(hipMemcpyAsync(FOpt, dFO, sizeof(double) * nm, hipMemcpyDeviceToHost, ctx->stream));
-        if (const int w = stream_wait(ctx->stream))
-            if (st == PNOL_OK) st = w;
-    }
-    if (dv) (void)hipFree(dv);
+    const HostArray arrays[] = {{(void*)ydata, nm, 8, kHostIn}, {X, np * n, 8, kHostIn | kHostOut},
+                                {chi0, np, 8, kHostOut},        {chi, np, 8, kHostOut},
+                                {evals, np, 8, kHostOut},       {iters, np, 4, kHostOut},
+                                {F0, nm, 8, kHostOut},          {FOpt, nm, 8, kHostOut}};
+    const int st = run_host_block(ctx, arrays, [&](void* const* d) {
+        return launch_lm_batch(ctx, b, (double*)d[0], params, (double*)d[1], (double*)d[2], (double*)d[3], (int*)d[5],
+                               (long long*)d[4], (double*)d[6], (double*)d[7]);
+    });
     pnol_lm_batch_destroy(b);
     return st;
 }
 
-}  // extern "C"
-
 // ---- batched Nelder-Mead (simplex_batch.hip) -----------------------------------------------
-namespace {
-
-// kind / size checks shared by the device- and the host-pointer call; nothing here touches a device
-int sxb_check_shape(int kind, int n, long long nstart) {
-    if (kind != PNOL_OBJ_ROSENBROCK && kind != PNOL_OBJ_POWER && kind != PNOL_OBJ_QUADRATIC)
-        return PNOL_ERR_UNSUPPORTED;
-    if (n <= 0 || nstart <= 0) return PNOL_ERR_ARG;
-    if (n > PNOL_SIMPLEX_BATCH_NMAX) return PNOL_ERR_UNSUPPORTED;
-    return PNOL_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int pnol_simplex_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* params, unsigned long long seed,
                                long long nstart, double* X, double* f0, double* fopt, int* iters, long long* evals) {
     if (!ctx || !obj) return PNOL_ERR_ARG;
     PNOL_CHECK(simplex_check_params(params));
-    PNOL_CHECK(sxb_check_shape(obj->kind, obj->n, nstart));
+    PNOL_CHECK(scalar_batch_check_shape(obj->kind, obj->n, nstart, PNOL_SIMPLEX_BATCH_NMAX));
     if (!X || !f0 || !fopt || !iters || !evals || obj->device != ctx->device) return PNOL_ERR_ARG;
     PNOL_CHECK(set_device(ctx));
     return launch_simplex_batch(ctx, obj, params, seed, nstart, X, f0, fopt, iters, evals);
@@ -737,7 +741,7 @@ int pnol_run_simplex_batch(int kind, int n, double power, const double* p0, size
                            size_t len1, long long nstart, const double* params, unsigned long long seed, double* X,
                            double* f0, double* fopt, int* iters, long long* evals) {
     PNOL_CHECK(simplex_check_params(params));
-    PNOL_CHECK(sxb_check_shape(kind, n, nstart));
+    PNOL_CHECK(scalar_batch_check_shape(kind, n, nstart, PNOL_SIMPLEX_BATCH_NMAX));
     if (kind == PNOL_OBJ_QUADRATIC && (!p0 || !p1 || len0 < (size_t)n || len1 < (size_t)n)) return PNOL_ERR_ARG;
     if (!X || !f0 || !fopt || !iters || !evals) return PNOL_ERR_ARG;
     pnol_ctx* ctx = nullptr;
@@ -746,57 +750,23 @@ int pnol_run_simplex_batch(int kind, int n, double power, const double* p0, size
     pnol_dobj* o = nullptr;
     PNOL_CHECK(pnol_dobj_create(ctx, kind, n, 0, p0, len0, p1, len1, power, &o));
     const size_t ns = (size_t)nstart;
-    // one device block: X | f0 | fopt | evals | iters (8-byte items first)
-    const size_t bytes = sizeof(double) * (ns * n + 2 * ns) + sizeof(long long) * ns + sizeof(int) * ns;
-    char* dv = nullptr;
-    int st = hipMalloc(&dv, bytes) == hipSuccess ? PNOL_OK : PNOL_ERR_NOMEM;
-    auto hip = [&](hipError_t e) {
-        if (st == PNOL_OK && e != hipSuccess) st = PNOL_ERR_HIP;
-    };
-    if (st == PNOL_OK) {
-        double* dX = (double*)dv;
-        double* df0 = dX + ns * n;
-        double* dfo = df0 + ns;
-        long long* dev = (long long*)(dfo + ns);
-        int* dit = (int*)(dev + ns);
-        hip(hipMemcpyAsync(dX, X, sizeof(double) * ns * n, hipMemcpyHostToDevice, ctx->stream));
-        if (st == PNOL_OK) st = launch_simplex_batch(ctx, o, params, seed, nstart, dX, df0, dfo, dit, dev);
-        hip(hipMemcpyAsync(X, dX, sizeof(double) * ns * n, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(f0, df0, sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(fopt, dfo, sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(evals, dev, sizeof(long long) * ns, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(iters, dit, sizeof(int) * ns, hipMemcpyDeviceToHost, ctx->stream));
-        if (const int w = stream_wait(ctx->stream))
-            if (st == PNOL_OK) st = w;
-    }
-    if (dv) (void)hipFree(dv);
+    const HostArray arrays[] = {{X, ns * n, 8, kHostIn | kHostOut}, {f0, ns, 8, kHostOut}, {fopt, ns, 8, kHostOut},
+                                {evals, ns, 8, kHostOut}, {iters, ns, 4, kHostOut}};
+    const int st = run_host_block(ctx, arrays, [&](void* const* d) {
+        return launch_simplex_batch(ctx, o, params, seed, nstart, (double*)d[0], (double*)d[1], (double*)d[2],
+                                    (int*)d[4], (long long*)d[3]);
+    });
     pnol_dobj_destroy(o);
     return st;
 }
 
-}  // extern "C"
-
 // ---- batched BFGS (bfgs_batch.hip) ---------------------------------------------------------
-namespace {
-
-// kind / size checks shared by the device- and the host-pointer call; nothing here touches a device
-int bfb_check_shape(int kind, int n, long long nstart) {
-    if (kind != PNOL_OBJ_ROSENBROCK && kind != PNOL_OBJ_POWER && kind != PNOL_OBJ_QUADRATIC)
-        return PNOL_ERR_UNSUPPORTED;
-    if (n <= 0 || nstart <= 0) return PNOL_ERR_ARG;
-    if (n > PNOL_BFGS_BATCH_NMAX) return PNOL_ERR_UNSUPPORTED;
-    return PNOL_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int pnol_bfgs_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* params, long long nstart, double* X,
                             double* f0, double* fopt, double* gnorm, int* iters, long long* evals) {
     if (!ctx || !obj) return PNOL_ERR_ARG;
     PNOL_CHECK(bfgs_batch_check_params(params));
-    PNOL_CHECK(bfb_check_shape(obj->kind, obj->n, nstart));
+    PNOL_CHECK(scalar_batch_check_shape(obj->kind, obj->n, nstart, PNOL_BFGS_BATCH_NMAX));
     if (!X || !f0 || !fopt || !gnorm || !iters || !evals || obj->device != ctx->device) return PNOL_ERR_ARG;
     PNOL_CHECK(set_device(ctx));
     return launch_bfgs_batch(ctx, obj, params, nstart, X, f0, fopt, gnorm, iters, evals);
@@ -806,7 +776,7 @@ int pnol_run_bfgs_batch(int kind, int n, double power, const double* p0, size_t 
                         long long nstart, const double* params, double* X, double* f0, double* fopt, double* gnorm,
                         int* iters, long long* evals) {
     PNOL_CHECK(bfgs_batch_check_params(params));
-    PNOL_CHECK(bfb_check_shape(kind, n, nstart));
+    PNOL_CHECK(scalar_batch_check_shape(kind, n, nstart, PNOL_BFGS_BATCH_NMAX));
     if (kind == PNOL_OBJ_QUADRATIC && (!p0 || !p1 || len0 < (size_t)n || len1 < (size_t)n)) return PNOL_ERR_ARG;
     if (!X || !f0 || !fopt || !gnorm || !iters || !evals) return PNOL_ERR_ARG;
     pnol_ctx* ctx = nullptr;
@@ -815,32 +785,12 @@ int pnol_run_bfgs_batch(int kind, int n, double power, const double* p0, size_t 
     pnol_dobj* o = nullptr;
     PNOL_CHECK(pnol_dobj_create(ctx, kind, n, 0, p0, len0, p1, len1, power, &o));
     const size_t ns = (size_t)nstart;
-    // one device block: X | f0 | fopt | gnorm | evals | iters (8-byte items first)
-    const size_t bytes = sizeof(double) * (ns * n + 3 * ns) + sizeof(long long) * ns + sizeof(int) * ns;
-    char* dv = nullptr;
-    int st = hipMalloc(&dv, bytes) == hipSuccess ? PNOL_OK : PNOL_ERR_NOMEM;
-    auto hip = [&](hipError_t e) {
-        if (st == PNOL_OK && e != hipSuccess) st = PNOL_ERR_HIP;
-    };
-    if (st == PNOL_OK) {
-        double* dX = (double*)dv;
-        double* df0 = dX + ns * n;
-        double* dfo = df0 + ns;
-        double* dgn = dfo + ns;
-        long long* dev = (long long*)(dgn + ns);
-        int* dit = (int*)(dev + ns);
-        hip(hipMemcpyAsync(dX, X, sizeof(double) * ns * n, hipMemcpyHostToDevice, ctx->stream));
-        if (st == PNOL_OK) st = launch_bfgs_batch(ctx, o, params, nstart, dX, df0, dfo, dgn, dit, dev);
-        hip(hipMemcpyAsync(X, dX, sizeof(double) * ns * n, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(f0, df0, sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(fopt, dfo, sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(gnorm, dgn, sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(evals, dev, sizeof(long long) * ns, hipMemcpyDeviceToHost, ctx->stream));
-        hip(hipMemcpyAsync(iters, dit, sizeof(int) * ns, hipMemcpyDeviceToHost, ctx->stream));
-        if (const int w = stream_wait(ctx->stream))
-            if (st == PNOL_OK) st = w;
-    }
-    if (dv) (void)hipFree(dv);
+    const HostArray arrays[] = {{X, ns * n, 8, kHostIn | kHostOut}, {f0, ns, 8, kHostOut},    {fopt, ns, 8, kHostOut},
+                                {gnorm, ns, 8, kHostOut},           {evals, ns, 8, kHostOut}, {iters, ns, 4, kHostOut}};
+    const int st = run_host_block(ctx, arrays, [&](void* const* d) {
+        return launch_bfgs_batch(ctx, o, params, nstart, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3],
+                                 (int*)d[5], (long long*)d[4]);
+    });
     pnol_dobj_destroy(o);
     return st;
 }

@@ -35,16 +35,15 @@
 // Rosenbrock, no difference on the quadratic; profiles/bfgs_batch_wait_ab.txt).  No cross-lane data, no
 // cross-workgroup waiting; a lane's work is bounded by maxIter * (4 maxIterLineSearch + n + 2)
 // evaluations.
-#include "../pnol_internal.hpp"
-#include "scalar_terms.hpp"
+#include "lane_batch.hpp"
 
 namespace pnol {
 namespace {
 
-constexpr int kBbLanes = 64;   // starts per workgroup: one wave
-
 // doubles of LDS per lane
 constexpr int bb_slots(int n) { return n * n + 6 * n; }
+static_assert(sizeof(double) * bb_slots(PNOL_BFGS_BATCH_NMAX) * kLaneBatchLanes <= kLaneBatchLdsMax,
+              "the largest problem's state must fit one CU's LDS");
 
 // what a lane does with the next objective value (states before BB_STEP evaluate)
 enum : int {
@@ -56,21 +55,6 @@ enum : int {
     BB_STEP,     // has its gradient: update D, loop test, next direction
     BB_DONE
 };
-
-// f at the point in the n slots from xs on (stride kBbLanes): the objective's sequential sum
-template <int KIND>
-__device__ __forceinline__ double bb_eval(const double* xs, int n, const double* __restrict__ p0,
-                                          const double* __restrict__ p1, double power) {
-    const int nt = scalar_nterms<KIND>(n);
-    double f = 0.0;
-    double xk = xs[0];
-    for (int k = 0; k < nt; ++k) {
-        const double xk1 = k + 1 < n ? xs[(k + 1) * kBbLanes] : 0.0;
-        f = f + scalar_term<KIND>(k, n, xk, xk1, p0, p1, power);
-        xk = xk1;
-    }
-    return f;
-}
 
 // cubicInterpMin (BFGS_with_linesearch.cpp:359-385); a zero bracket width and the NaN that
 // follows are what IEEE gives, as on the host
@@ -89,33 +73,30 @@ __device__ __forceinline__ double bb_cubic(double alo, double ahi, double plo, d
 }
 
 template <int KIND>
-__global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, const double* __restrict__ p0,
-                                                         const double* __restrict__ p1, double power, double c1,
-                                                         double c2, double dalpha, double alphaGuess, int maxIterLS,
-                                                         double dXGrad, int maxIter, double xMinDiff,
-                                                         double minGrad2Norm, double* __restrict__ Xio,
-                                                         double* __restrict__ f0out, double* __restrict__ fopt,
-                                                         double* __restrict__ gnout, int* __restrict__ iters,
-                                                         long long* __restrict__ evals) {
+__global__ __launch_bounds__(kLaneBatchLanes) void k_bfgs_batch(
+    int n, size_t nstart, const double* __restrict__ p0, const double* __restrict__ p1, double power, double c1,
+    double c2, double dalpha, double alphaGuess, int maxIterLS, double dXGrad, int maxIter, double xMinDiff,
+    double minGrad2Norm, double* __restrict__ Xio, double* __restrict__ f0out, double* __restrict__ fopt,
+    double* __restrict__ gnout, int* __restrict__ iters, long long* __restrict__ evals) {
     extern __shared__ __attribute__((aligned(16))) double bb_lds[];
     const int lane = threadIdx.x;
-    const size_t s = (size_t)blockIdx.x * kBbLanes + lane;
+    const size_t s = (size_t)blockIdx.x * kLaneBatchLanes + lane;
     const bool valid = s < nstart;
     double* const D = bb_lds + lane;               // D_ij at (i * n + j)
-    double* const X = D + n * n * kBbLanes;
-    double* const g = X + n * kBbLanes;
-    double* const gp = g + n * kBbLanes;           // gprev; y inside the update
-    double* const p = gp + n * kBbLanes;           // p; s inside the update
-    double* const xt = p + n * kBbLanes;           // the point the next value is taken at
-    double* const tmp = xt + n * kBbLanes;
+    double* const X = D + n * n * kLaneBatchLanes;
+    double* const g = X + n * kLaneBatchLanes;
+    double* const gp = g + n * kLaneBatchLanes;           // gprev; y inside the update
+    double* const p = gp + n * kLaneBatchLanes;           // p; s inside the update
+    double* const xt = p + n * kLaneBatchLanes;           // the point the next value is taken at
+    double* const tmp = xt + n * kLaneBatchLanes;
 
     for (int j = 0; j < n; ++j) {
         const double x = valid ? Xio[s * (size_t)n + j] : 0.0;
-        X[j * kBbLanes] = x;
-        xt[j * kBbLanes] = x;
+        X[j * kLaneBatchLanes] = x;
+        xt[j * kLaneBatchLanes] = x;
     }
     for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) D[(i * n + j) * kBbLanes] = i == j ? 1.0 : 0.0;
+        for (int j = 0; j < n; ++j) D[(i * n + j) * kLaneBatchLanes] = i == j ? 1.0 : 0.0;
 
     int state = valid ? BB_GBASE : BB_DONE;
     bool first = true;    // the gradient in flight is the one before the loop (:40-45)
@@ -132,7 +113,7 @@ __global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, c
     while (__any(state != BB_DONE)) {
         double v = 0.0;
         if (state < BB_STEP) {
-            v = bb_eval<KIND>(xt, n, p0, p1, power);
+            v = lane_eval<KIND>(xt, n, p0, p1, power);
             ++ev;
         }
         bool lsDone = false;
@@ -143,10 +124,10 @@ __global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, c
             xt[0] = X[0] + dXGrad;
             state = BB_GCOORD;
         } else if (state == BB_GCOORD) {
-            g[ci * kBbLanes] = (v - Fb) / dXGrad;
-            xt[ci * kBbLanes] = X[ci * kBbLanes];
+            g[ci * kLaneBatchLanes] = (v - Fb) / dXGrad;
+            xt[ci * kLaneBatchLanes] = X[ci * kLaneBatchLanes];
             ++ci;
-            if (ci < n) xt[ci * kBbLanes] = X[ci * kBbLanes] + dXGrad;
+            if (ci < n) xt[ci * kLaneBatchLanes] = X[ci * kLaneBatchLanes] + dXGrad;
             else state = first ? BB_F0 : BB_STEP;
         } else if (state == BB_F0) {
             F = v;
@@ -156,7 +137,7 @@ __global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, c
             // lineSearchObj gave phi(ac); lineSearchFDDerivative's point (:160-174)
             pc = v;
             const double a2 = ac + dalpha;
-            for (int i = 0; i < n; ++i) xt[i * kBbLanes] = X[i * kBbLanes] + a2 * p[i * kBbLanes];
+            for (int i = 0; i < n; ++i) xt[i * kLaneBatchLanes] = X[i * kLaneBatchLanes] + a2 * p[i * kLaneBatchLanes];
             state = BB_LS_B;
         } else if (state == BB_LS_B) {
             const double dc = (v - pc) / dalpha;
@@ -198,7 +179,8 @@ __global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, c
             }
             if (!lsDone) {
                 if (zoom) ac = bb_cubic(alo, ahi, plo, phi, dlo, dhi);
-                for (int i = 0; i < n; ++i) xt[i * kBbLanes] = X[i * kBbLanes] + ac * p[i * kBbLanes];
+                for (int i = 0; i < n; ++i)
+                    xt[i * kLaneBatchLanes] = X[i * kLaneBatchLanes] + ac * p[i * kLaneBatchLanes];
                 state = BB_LS_A;
             }
         }
@@ -214,41 +196,41 @@ __global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, c
                 // s = alpha p and y = g - gprev (:113-114); updateHessianInv (:389-432)
                 double ys = 0.0;
                 for (int i = 0; i < n; ++i) {
-                    const double si = alpha * p[i * kBbLanes];
-                    const double yi = g[i * kBbLanes] - gp[i * kBbLanes];
-                    p[i * kBbLanes] = si;
-                    gp[i * kBbLanes] = yi;
+                    const double si = alpha * p[i * kLaneBatchLanes];
+                    const double yi = g[i * kLaneBatchLanes] - gp[i * kLaneBatchLanes];
+                    p[i * kLaneBatchLanes] = si;
+                    gp[i * kLaneBatchLanes] = yi;
                     ys = ys + yi * si;
                 }
                 const double rho = 1 / ys;
                 for (int j = 0; j < n; ++j) {          // column j of M1 D
                     for (int i = 0; i < n; ++i) {
-                        const double rs = rho * p[i * kBbLanes];
+                        const double rs = rho * p[i * kLaneBatchLanes];
                         double acc = 0.0;
                         for (int l = 0; l < n; ++l) {
                             const double e = i == l ? 1.0 : 0.0;
-                            acc = acc + (e - rs * gp[l * kBbLanes]) * D[(l * n + j) * kBbLanes];
+                            acc = acc + (e - rs * gp[l * kLaneBatchLanes]) * D[(l * n + j) * kLaneBatchLanes];
                         }
-                        tmp[i * kBbLanes] = acc;
+                        tmp[i * kLaneBatchLanes] = acc;
                     }
-                    for (int i = 0; i < n; ++i) D[(i * n + j) * kBbLanes] = tmp[i * kBbLanes];
+                    for (int i = 0; i < n; ++i) D[(i * n + j) * kLaneBatchLanes] = tmp[i * kLaneBatchLanes];
                 }
                 for (int i = 0; i < n; ++i) {          // row i of (M1 D) M2, + M3
                     for (int j = 0; j < n; ++j) {
-                        const double sj = p[j * kBbLanes];
+                        const double sj = p[j * kLaneBatchLanes];
                         double acc = 0.0;
                         for (int l = 0; l < n; ++l) {
                             const double e = l == j ? 1.0 : 0.0;
-                            acc = acc + D[(i * n + l) * kBbLanes] * (e - rho * gp[l * kBbLanes] * sj);
+                            acc = acc + D[(i * n + l) * kLaneBatchLanes] * (e - rho * gp[l * kLaneBatchLanes] * sj);
                         }
-                        tmp[j * kBbLanes] = acc;
+                        tmp[j * kLaneBatchLanes] = acc;
                     }
-                    const double rs = rho * p[i * kBbLanes];
+                    const double rs = rho * p[i * kLaneBatchLanes];
                     for (int j = 0; j < n; ++j)
-                        D[(i * n + j) * kBbLanes] = tmp[j * kBbLanes] + rs * p[j * kBbLanes];
+                        D[(i * n + j) * kLaneBatchLanes] = tmp[j * kLaneBatchLanes] + rs * p[j * kLaneBatchLanes];
                 }
                 double gg = 0.0;
-                for (int i = 0; i < n; ++i) gg = gg + g[i * kBbLanes] * g[i * kBbLanes];
+                for (int i = 0; i < n; ++i) gg = gg + g[i * kLaneBatchLanes] * g[i * kLaneBatchLanes];
                 gnorm = sqrt(gg);
                 ++iter;
             }
@@ -256,13 +238,13 @@ __global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, c
             if (iter < maxIter && xdiff > xMinDiff && gnorm > minGrad2Norm) {
                 // p = -D g (:52-56), then the line search's start (:177-190)
                 for (int i = 0; i < n; ++i) {
-                    gp[i * kBbLanes] = g[i * kBbLanes];
+                    gp[i * kLaneBatchLanes] = g[i * kLaneBatchLanes];
                     double acc = 0.0;
-                    for (int j = 0; j < n; ++j) acc = acc + D[(i * n + j) * kBbLanes] * g[j * kBbLanes];
-                    p[i * kBbLanes] = -acc;
+                    for (int j = 0; j < n; ++j) acc = acc + D[(i * n + j) * kLaneBatchLanes] * g[j * kLaneBatchLanes];
+                    p[i * kLaneBatchLanes] = -acc;
                 }
                 double gd = 0.0;
-                for (int i = 0; i < n; ++i) gd = gd + g[i * kBbLanes] * p[i * kBbLanes];
+                for (int i = 0; i < n; ++i) gd = gd + g[i * kLaneBatchLanes] * p[i * kLaneBatchLanes];
                 alpha = 0.0; Fopt = F;
                 phi0 = F; dphi0 = gd;
                 alo = 0.0; plo = phi0; dlo = dphi0;
@@ -270,7 +252,8 @@ __global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, c
                 it = 0;
                 zoom = false;
                 if (it < maxIterLS) {
-                    for (int i = 0; i < n; ++i) xt[i * kBbLanes] = X[i * kBbLanes] + ac * p[i * kBbLanes];
+                    for (int i = 0; i < n; ++i)
+                        xt[i * kLaneBatchLanes] = X[i * kLaneBatchLanes] + ac * p[i * kLaneBatchLanes];
                     state = BB_LS_A;
                 } else {
                     lsDone = true;
@@ -284,10 +267,10 @@ __global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, c
             // X <- X + alpha p, xdiff = sum |X - Xprev| (:100-125), then the gradient at the new X
             double xd = 0.0;
             for (int i = 0; i < n; ++i) {
-                const double xo = X[i * kBbLanes];
-                const double xn = xo + alpha * p[i * kBbLanes];
-                X[i * kBbLanes] = xn;
-                xt[i * kBbLanes] = xn;
+                const double xo = X[i * kLaneBatchLanes];
+                const double xn = xo + alpha * p[i * kLaneBatchLanes];
+                X[i * kLaneBatchLanes] = xn;
+                xt[i * kLaneBatchLanes] = xn;
                 xd += fabs(xn - xo);
             }
             xdiff = xd;
@@ -297,7 +280,7 @@ __global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, c
     }
 
     if (valid) {
-        for (int j = 0; j < n; ++j) Xio[s * (size_t)n + j] = X[j * kBbLanes];
+        for (int j = 0; j < n; ++j) Xio[s * (size_t)n + j] = X[j * kLaneBatchLanes];
         f0out[s] = f0;
         fopt[s] = F;
         gnout[s] = gnorm;
@@ -306,41 +289,19 @@ __global__ __launch_bounds__(kBbLanes) void k_bfgs_batch(int n, size_t nstart, c
     }
 }
 
-template <int KIND>
-int bb_launch(pnol_ctx* ctx, const pnol_dobj* o, const double* prm, size_t nstart, double* X, double* f0, double* fopt,
-              double* gnorm, int* iters, long long* evals) {
-    const size_t lds = sizeof(double) * (size_t)bb_slots(o->n) * kBbLanes;
-    auto* kern = &k_bfgs_batch<KIND>;
-    if (lds > 64 * 1024)
-        PNOL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
-    const size_t blocks = (nstart + kBbLanes - 1) / kBbLanes;
-    ScopedTimer tm(ctx, "bfgs_batch");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBbLanes), lds, ctx->stream, o->n, nstart,
-                       (const double*)o->p0, (const double*)o->p1, o->power, prm[0], prm[1], prm[2], prm[3],
-                       (int)prm[4], prm[5], (int)prm[7], prm[8], prm[9], X, f0, fopt, gnorm, iters, evals);
-    return launch_check();
-}
-
 }  // namespace
 
 int launch_bfgs_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, long long nstart, double* X,
                       double* f0, double* fopt, double* gnorm, int* iters, long long* evals) {
-    if (!ctx || !o || !params || !X || !f0 || !fopt || !gnorm || !iters || !evals || nstart <= 0) return PNOL_ERR_ARG;
-    if (o->n < 1) return PNOL_ERR_ARG;
-    if (o->n > PNOL_BFGS_BATCH_NMAX) return PNOL_ERR_UNSUPPORTED;
-    if (((size_t)nstart + kBbLanes - 1) / kBbLanes > 0x7fffffffull) return PNOL_ERR_ARG;
-    if (o->kind == PNOL_OBJ_QUADRATIC && (o->len0 < (size_t)o->n || o->len1 < (size_t)o->n)) return PNOL_ERR_ARG;
-    switch (o->kind) {
-        case PNOL_OBJ_ROSENBROCK:
-            return bb_launch<PNOL_OBJ_ROSENBROCK>(ctx, o, params, (size_t)nstart, X, f0, fopt, gnorm, iters, evals);
-        case PNOL_OBJ_POWER:
-            return bb_launch<PNOL_OBJ_POWER>(ctx, o, params, (size_t)nstart, X, f0, fopt, gnorm, iters, evals);
-        case PNOL_OBJ_QUADRATIC:
-            return bb_launch<PNOL_OBJ_QUADRATIC>(ctx, o, params, (size_t)nstart, X, f0, fopt, gnorm, iters, evals);
-        default:
-            return PNOL_ERR_UNSUPPORTED;
-    }
+    if (!ctx || !params || !X || !f0 || !fopt || !gnorm || !iters || !evals || nstart <= 0) return PNOL_ERR_ARG;
+    PNOL_CHECK(scalar_batch_check(o, PNOL_BFGS_BATCH_NMAX));
+    const double* p = params;
+    const size_t ns = (size_t)nstart, lds = sizeof(double) * (size_t)bb_slots(o->n) * kLaneBatchLanes;
+    return scalar_batch_dispatch(o->kind, [&](auto kind) {
+        return lane_batch_launch(ctx, "bfgs_batch", &k_bfgs_batch<decltype(kind)::value>, ns, lds, o->n, ns,
+                                 (const double*)o->p0, (const double*)o->p1, o->power, p[0], p[1], p[2], p[3],
+                                 (int)p[4], p[5], (int)p[7], p[8], p[9], X, f0, fopt, gnorm, iters, evals);
+    });
 }
 
 }  // namespace pnol

@@ -21,8 +21,8 @@
 // per-problem x grids and their cube tables are staged the same way, a shared grid is read at a
 // wave-uniform address.  Small problems are staged once and stay resident for the whole solve
 // (kLmbResident); larger ones are re-staged in kLmbRows-row chunks, twice per trip, from L2.
-#include "../pnol_internal.hpp"
 #include "../pnol_env.hpp"
+#include "lane_batch.hpp"
 #include "multi_residual.hpp"
 
 #include <cstdlib>
@@ -30,9 +30,7 @@
 namespace pnol {
 namespace {
 
-constexpr int kLmbLanes = 64;               // problems per workgroup: one wave
-constexpr int kLmbRows = 32;                // data rows staged per chunk
-constexpr size_t kLmbLdsMax = 160 * 1024;   // LDS of one CU
+constexpr int kLmbRows = 32;   // data rows staged per chunk
 // Rows stay resident in LDS for the whole solve when that takes at most this much of it: the
 // footprint of the measured case (m = 100 on a shared grid: 64 x 101 doubles, three waves per
 // CU), which took 12-18% less time than re-staging 32-row chunks twice per trip
@@ -49,7 +47,7 @@ struct LmbDim {
 __device__ __forceinline__ void lmb_stage(double* __restrict__ dst, const double* __restrict__ src, size_t p0,
                                           size_t nprob, int m, int c0, int len, int stride) {
     const int sub = threadIdx.x & 15, qq = threadIdx.x >> 4;
-    for (int q = qq; q < kLmbLanes; q += 4) {
+    for (int q = qq; q < kLaneBatchLanes; q += 4) {
         const size_t p = p0 + q;
         const bool in = p < nprob;
         const double* s = src + (in ? p * (size_t)m + c0 : 0);
@@ -59,22 +57,20 @@ __device__ __forceinline__ void lmb_stage(double* __restrict__ dst, const double
 
 // PERX: per-problem x grids (xg / p3g hold nprob * m values), else one shared grid of m.
 template <int KIND, bool PERX>
-__global__ __launch_bounds__(kLmbLanes) void k_lm_batch(const double* __restrict__ xg, const double* __restrict__ p3g,
-                                                        const double* __restrict__ yg, int m, size_t nprob, int R,
-                                                        int stride, double lambda0, double factor, double h,
-                                                        int maxIter, double xMinDiff, double* __restrict__ Xio,
-                                                        double* __restrict__ chi0, double* __restrict__ chi,
-                                                        int* __restrict__ iters, long long* __restrict__ evals,
-                                                        double* __restrict__ F0, double* __restrict__ FOpt) {
+__global__ __launch_bounds__(kLaneBatchLanes) void k_lm_batch(
+    const double* __restrict__ xg, const double* __restrict__ p3g, const double* __restrict__ yg, int m, size_t nprob,
+    int R, int stride, double lambda0, double factor, double h, int maxIter, double xMinDiff,
+    double* __restrict__ Xio, double* __restrict__ chi0, double* __restrict__ chi, int* __restrict__ iters,
+    long long* __restrict__ evals, double* __restrict__ F0, double* __restrict__ FOpt) {
     constexpr int N = LmbDim<KIND>::n;
     constexpr bool kCubic = KIND == PNOL_OBJ_CUBIC;
     if (R < 1) return;   // the row loops step by R (the launcher never passes less; uniform)
     extern __shared__ double lmb_lds[];
     double* ys = lmb_lds;
-    double* xs = ys + kLmbLanes * stride;    // PERX only
-    double* ps = xs + kLmbLanes * stride;    // PERX && Cubic only
+    double* xs = ys + kLaneBatchLanes * stride;    // PERX only
+    double* ps = xs + kLaneBatchLanes * stride;    // PERX && Cubic only
     const int lane = threadIdx.x;
-    const size_t p0 = (size_t)blockIdx.x * kLmbLanes, p = p0 + lane;
+    const size_t p0 = (size_t)blockIdx.x * kLaneBatchLanes, p = p0 + lane;
     const bool valid = p < nprob;
     const bool resident = R >= m;   // one chunk: staged once, kept for the whole solve
 
@@ -283,25 +279,17 @@ template <int KIND, bool PERX>
 int lmb_launch(pnol_ctx* ctx, const pnol_lm_batch* b, const double* y, const double* prm, double* X, double* chi0,
                double* chi, int* iters, long long* evals, double* F0, double* FOpt) {
     const int narr = 1 + (PERX ? (KIND == PNOL_OBJ_CUBIC ? 2 : 1) : 0);
-    auto lds_bytes = [&](int rows) { return sizeof(double) * (size_t)narr * kLmbLanes * (size_t)(rows | 1); };
+    auto lds_bytes = [&](int rows) { return sizeof(double) * (size_t)narr * kLaneBatchLanes * (size_t)(rows | 1); };
     // all m rows resident when they fit kLmbResident of LDS, else kLmbRows-row chunks; a
     // PNOL_LMB_ROWS chunk that would not fit the CU's LDS is not taken
     const int want = lmb_rows_env();   // >= 1: the environment's chunk or kLmbRows
     int R = lmb_rows_set() ? want : (lds_bytes(b->m) <= kLmbResident ? b->m : kLmbRows);
     R = std::min(R, b->m);
-    if (lds_bytes(R) > kLmbLdsMax) R = std::min(kLmbRows, b->m);
+    if (lds_bytes(R) > kLaneBatchLdsMax) R = std::min(kLmbRows, b->m);
     if (R < 1 || b->m < 1) return PNOL_ERR_ARG;   // the kernel's row loops step by R
-    const size_t lds = lds_bytes(R);
-    auto* kern = &k_lm_batch<KIND, PERX>;
-    if (lds > 64 * 1024)
-        PNOL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
-    const size_t blocks = (b->nprob + kLmbLanes - 1) / kLmbLanes;
-    ScopedTimer tm(ctx, "lm_batch");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kLmbLanes), lds, ctx->stream, (const double*)b->x,
-                       (const double*)b->p3, y, b->m, b->nprob, R, R | 1, prm[0], prm[1], prm[2], (int)prm[3], prm[4], X,
-                       chi0, chi, iters, evals, F0, FOpt);
-    return launch_check();
+    return lane_batch_launch(ctx, "lm_batch", &k_lm_batch<KIND, PERX>, b->nprob, lds_bytes(R), (const double*)b->x,
+                             (const double*)b->p3, y, b->m, b->nprob, R, R | 1, prm[0], prm[1], prm[2], (int)prm[3],
+                             prm[4], X, chi0, chi, iters, evals, F0, FOpt);
 }
 
 }  // namespace
@@ -309,7 +297,7 @@ int lmb_launch(pnol_ctx* ctx, const pnol_lm_batch* b, const double* y, const dou
 int launch_lm_batch(pnol_ctx* ctx, const pnol_lm_batch* b, const double* y, const double* params, double* X,
                     double* chi0, double* chi, int* iters, long long* evals, double* F0, double* FOpt) {
     if (!ctx || !b || !y || !params || !X || !chi0 || !chi || !iters || !evals) return PNOL_ERR_ARG;
-    if (b->nprob == 0 || (b->nprob + kLmbLanes - 1) / kLmbLanes > 0x7fffffffull) return PNOL_ERR_ARG;
+    if (b->nprob == 0) return PNOL_ERR_ARG;
     const bool px = b->per_problem_x;
     if (b->kind == PNOL_OBJ_EXPCURVE)
         return px ? lmb_launch<PNOL_OBJ_EXPCURVE, true>(ctx, b, y, params, X, chi0, chi, iters, evals, F0, FOpt)

@@ -1,6 +1,7 @@
 // scalar_terms.hpp -- term k of the built-in scalar objectives (Rosenbrock, Power, the synthetic
 // quadratic), the one definition every kernel that evaluates them compiles (fd.hip: the FD
-// gradient's term form; simplex_batch.hip: one lane per search).  f = sum_k t_k accumulated in k
+// gradient's term form; simplex_batch.hip and bfgs_batch.hip: one lane per search, through
+// lane_batch.hpp's lane_eval).  f = sum_k t_k accumulated in k
 // order is the objective's own sequential sum; plain + and * in the objective's operation order
 // and -ffp-contract=off, so the same point gives the same bits in every kernel and on the host
 // (host/scalar_host.hpp).

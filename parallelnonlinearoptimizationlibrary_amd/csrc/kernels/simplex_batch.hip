@@ -27,31 +27,16 @@
 // call sites the lanes reach together: every active lane's reflection, then the second point of
 // every lane that needs one (expansion or contraction), then the n + 1 vertices of the rare
 // lanes that shrink.
-#include "../pnol_internal.hpp"
-#include "scalar_terms.hpp"
+#include "lane_batch.hpp"
 
 namespace pnol {
 namespace {
 
-constexpr int kSxLanes = 64;   // starts per workgroup: one wave
-
 // doubles of LDS per lane
 constexpr int sx_slots(int n) { return (n + 1) * (n + 1) + 3 * n; }
-
-// f at the point in the n slots from xs on (stride kSxLanes): the objective's sequential sum
-template <int KIND>
-__device__ __forceinline__ double sx_eval(const double* xs, int n, const double* __restrict__ p0,
-                                          const double* __restrict__ p1, double power) {
-    const int nt = scalar_nterms<KIND>(n);
-    double f = 0.0;
-    double xk = xs[0];
-    for (int k = 0; k < nt; ++k) {
-        const double xk1 = k + 1 < n ? xs[(k + 1) * kSxLanes] : 0.0;
-        f = f + scalar_term<KIND>(k, n, xk, xk1, p0, p1, power);
-        xk = xk1;
-    }
-    return f;
-}
+static_assert(sizeof(double) * sx_slots(PNOL_SIMPLEX_BATCH_NMAX) * kLaneBatchLanes <= kLaneBatchLdsMax,
+              "the largest simplex must fit one CU's LDS");
+static_assert(4 * (PNOL_SIMPLEX_BATCH_NMAX + 1) <= 64, "one nibble per sorted position in the 64-bit permutation");
 
 // physical row at sorted position k
 __device__ __forceinline__ int sx_row(unsigned long long perm, int k) { return (int)((perm >> (4 * k)) & 15ull); }
@@ -61,12 +46,12 @@ __device__ __forceinline__ int sx_row(unsigned long long perm, int k) { return (
 __device__ __forceinline__ void sx_insert(double* fv, unsigned long long& perm, int k, double v) {
     int p = k;
     while (p > 0) {
-        const double prev = fv[(p - 1) * kSxLanes];
+        const double prev = fv[(p - 1) * kLaneBatchLanes];
         if (!(prev > v)) break;
-        fv[p * kSxLanes] = prev;
+        fv[p * kLaneBatchLanes] = prev;
         --p;
     }
-    fv[p * kSxLanes] = v;
+    fv[p * kLaneBatchLanes] = v;
     if (p != k) {
         const unsigned long long r = (perm >> (4 * k)) & 15ull;
         const unsigned long long lo = (1ull << (4 * p)) - 1ull;            // positions < p
@@ -77,27 +62,25 @@ __device__ __forceinline__ void sx_insert(double* fv, unsigned long long& perm, 
 }
 
 template <int KIND>
-__global__ __launch_bounds__(kSxLanes) void k_simplex_batch(int n, size_t nstart, const double* __restrict__ p0,
-                                                            const double* __restrict__ p1, double power, double alpha,
-                                                            double gamma, double rho, double sigma, int maxIter,
-                                                            double initRandMax, double xMinDiff,
-                                                            unsigned long long seed, double* __restrict__ Xio,
-                                                            double* __restrict__ f0out, double* __restrict__ fopt,
-                                                            int* __restrict__ iters, long long* __restrict__ evals) {
+__global__ __launch_bounds__(kLaneBatchLanes) void k_simplex_batch(
+    int n, size_t nstart, const double* __restrict__ p0, const double* __restrict__ p1, double power, double alpha,
+    double gamma, double rho, double sigma, int maxIter, double initRandMax, double xMinDiff, unsigned long long seed,
+    double* __restrict__ Xio, double* __restrict__ f0out, double* __restrict__ fopt, int* __restrict__ iters,
+    long long* __restrict__ evals) {
     extern __shared__ __attribute__((aligned(16))) double sx_lds[];
     const int lane = threadIdx.x;
-    const size_t s = (size_t)blockIdx.x * kSxLanes + lane;
+    const size_t s = (size_t)blockIdx.x * kLaneBatchLanes + lane;
     const bool valid = s < nstart;
     double* const xv = sx_lds + lane;                   // vertices: row r, coordinate j at (r * n + j)
-    double* const fv = xv + (n + 1) * n * kSxLanes;     // values by sorted position
-    double* const xbar = fv + (n + 1) * kSxLanes;
-    double* const xref = xbar + n * kSxLanes;
-    double* const x2 = xref + n * kSxLanes;
+    double* const fv = xv + (n + 1) * n * kLaneBatchLanes;     // values by sorted position
+    double* const xbar = fv + (n + 1) * kLaneBatchLanes;
+    double* const xref = xbar + n * kLaneBatchLanes;
+    double* const x2 = xref + n * kLaneBatchLanes;
     const double dn = (double)n;
 
     // the initial simplex (SimplexSearch.cpp:46-67): vertex 0 is X, vertex i >= 1 adds
     // initRandMax * (u - 0.5) * 2.0 per coordinate, one draw per (i, j), i outer
-    for (int j = 0; j < n; ++j) xv[j * kSxLanes] = valid ? Xio[s * (size_t)n + j] : 0.0;
+    for (int j = 0; j < n; ++j) xv[j * kLaneBatchLanes] = valid ? Xio[s * (size_t)n + j] : 0.0;
     unsigned long long state = seed + (unsigned long long)s;
     for (int i = 1; i <= n; ++i)
         for (int j = 0; j < n; ++j) {
@@ -106,13 +89,13 @@ __global__ __launch_bounds__(kSxLanes) void k_simplex_batch(int n, size_t nstart
             z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
             z ^= z >> 31;
             const double u = (double)(z >> 11) * 0x1.0p-53;
-            xv[(i * n + j) * kSxLanes] = xv[j * kSxLanes] + initRandMax * (u - 0.5) * 2.0;
+            xv[(i * n + j) * kLaneBatchLanes] = xv[j * kLaneBatchLanes] + initRandMax * (u - 0.5) * 2.0;
         }
     // all n + 1 vertices, f0 = the value of vertex 0, sort (:70-75)
     unsigned long long perm = 0xFEDCBA9876543210ull;
     double f0 = 0.0;
     for (int k = 0; k <= n; ++k) {
-        const double v = sx_eval<KIND>(xv + k * n * kSxLanes, n, p0, p1, power);
+        const double v = lane_eval<KIND>(xv + k * n * kLaneBatchLanes, n, p0, p1, power);
         if (k == 0) f0 = v;
         sx_insert(fv, perm, k, v);
     }
@@ -122,65 +105,65 @@ __global__ __launch_bounds__(kSxLanes) void k_simplex_batch(int n, size_t nstart
     bool active = valid && iter < maxIter && xdiff > xMinDiff;
 
     while (__any(active)) {
-        double* const xw = xv + sx_row(perm, n) * n * kSxLanes;   // the worst vertex
+        double* const xw = xv + sx_row(perm, n) * n * kLaneBatchLanes;   // the worst vertex
         // ---- phase 1: centroid of the n best, reflection (:90-110)
         double fref = 0.0;
         if (active) {
             for (int i = 0; i < n; ++i) {
                 double xb = 0.0;
-                for (int k = 0; k < n; ++k) xb = xb + xv[(sx_row(perm, k) * n + i) * kSxLanes] / dn;
-                xbar[i * kSxLanes] = xb;
-                xref[i * kSxLanes] = xb + alpha * (xb - xw[i * kSxLanes]);
+                for (int k = 0; k < n; ++k) xb = xb + xv[(sx_row(perm, k) * n + i) * kLaneBatchLanes] / dn;
+                xbar[i * kLaneBatchLanes] = xb;
+                xref[i * kLaneBatchLanes] = xb + alpha * (xb - xw[i * kLaneBatchLanes]);
             }
-            fref = sx_eval<KIND>(xref, n, p0, p1, power);
+            fref = lane_eval<KIND>(xref, n, p0, p1, power);
         }
         // ---- phase 2: expansion or contraction (:115-166)
-        const double fbest = fv[0], fsecond = fv[(n - 1) * kSxLanes], fworst = fv[n * kSxLanes];
+        const double fbest = fv[0], fsecond = fv[(n - 1) * kLaneBatchLanes], fworst = fv[n * kLaneBatchLanes];
         const bool keepRef = active && fref >= fbest && fref < fsecond;
         const bool expand = active && !keepRef && fref < fbest;
         const bool second = active && !keepRef;
         double f2 = 0.0;
         if (second) {
             for (int i = 0; i < n; ++i) {
-                const double xb = xbar[i * kSxLanes], w = xw[i * kSxLanes];
-                x2[i * kSxLanes] = expand ? xb + gamma * (xb - w) : xb + rho * (w - xb);
+                const double xb = xbar[i * kLaneBatchLanes], w = xw[i * kLaneBatchLanes];
+                x2[i * kLaneBatchLanes] = expand ? xb + gamma * (xb - w) : xb + rho * (w - xb);
             }
-            f2 = sx_eval<KIND>(x2, n, p0, p1, power);
+            f2 = lane_eval<KIND>(x2, n, p0, p1, power);
         }
         const bool take2 = second && (expand ? f2 < fref : f2 < fworst);
         const bool shrink = second && !expand && !take2;
         if (active && !shrink) {
             // the worst vertex is replaced and takes its sorted place (:117-173, :194)
             const double* src = take2 ? x2 : xref;
-            for (int i = 0; i < n; ++i) xw[i * kSxLanes] = src[i * kSxLanes];
+            for (int i = 0; i < n; ++i) xw[i * kLaneBatchLanes] = src[i * kLaneBatchLanes];
             sx_insert(fv, perm, n, take2 ? f2 : fref);
         }
         // ---- phase 3: shrink toward the best vertex, all n + 1 re-evaluated (:178-188)
         if (__any(shrink)) {
-            const double* const x0 = xv + sx_row(perm, 0) * n * kSxLanes;
+            const double* const x0 = xv + sx_row(perm, 0) * n * kLaneBatchLanes;
             if (shrink)
                 for (int k = 1; k <= n; ++k) {
-                    double* const xk = xv + sx_row(perm, k) * n * kSxLanes;
+                    double* const xk = xv + sx_row(perm, k) * n * kLaneBatchLanes;
                     for (int i = 0; i < n; ++i) {
-                        const double b = x0[i * kSxLanes];
-                        xk[i * kSxLanes] = b + sigma * (xk[i * kSxLanes] - b);
+                        const double b = x0[i * kLaneBatchLanes];
+                        xk[i * kLaneBatchLanes] = b + sigma * (xk[i * kLaneBatchLanes] - b);
                     }
                 }
             for (int k = 0; k <= n; ++k)
                 if (shrink) {
-                    const double v = sx_eval<KIND>(xv + sx_row(perm, k) * n * kSxLanes, n, p0, p1, power);
+                    const double v = lane_eval<KIND>(xv + sx_row(perm, k) * n * kLaneBatchLanes, n, p0, p1, power);
                     sx_insert(fv, perm, k, v);
                 }
         }
         if (active) {
             ev += 1 + (second ? 1 : 0) + (shrink ? n + 1 : 0);
             // xdiff = max |x0 - xk| over k >= 1 (simplexDiff, :331-349)
-            const double* const x0 = xv + sx_row(perm, 0) * n * kSxLanes;
+            const double* const x0 = xv + sx_row(perm, 0) * n * kLaneBatchLanes;
             double d = 0.0;
             for (int k = 1; k <= n; ++k) {
-                const double* const xk = xv + sx_row(perm, k) * n * kSxLanes;
+                const double* const xk = xv + sx_row(perm, k) * n * kLaneBatchLanes;
                 for (int i = 0; i < n; ++i) {
-                    const double diff = fabs(x0[i * kSxLanes] - xk[i * kSxLanes]);
+                    const double diff = fabs(x0[i * kLaneBatchLanes] - xk[i * kLaneBatchLanes]);
                     if (diff > d) d = diff;
                 }
             }
@@ -191,8 +174,8 @@ __global__ __launch_bounds__(kSxLanes) void k_simplex_batch(int n, size_t nstart
     }
 
     if (valid) {
-        const double* const x0 = xv + sx_row(perm, 0) * n * kSxLanes;
-        for (int j = 0; j < n; ++j) Xio[s * (size_t)n + j] = x0[j * kSxLanes];
+        const double* const x0 = xv + sx_row(perm, 0) * n * kLaneBatchLanes;
+        for (int j = 0; j < n; ++j) Xio[s * (size_t)n + j] = x0[j * kLaneBatchLanes];
         f0out[s] = f0;
         fopt[s] = fv[0];
         iters[s] = iter;
@@ -200,41 +183,19 @@ __global__ __launch_bounds__(kSxLanes) void k_simplex_batch(int n, size_t nstart
     }
 }
 
-template <int KIND>
-int sx_launch(pnol_ctx* ctx, const pnol_dobj* o, const double* prm, unsigned long long seed, size_t nstart, double* X,
-              double* f0, double* fopt, int* iters, long long* evals) {
-    const size_t lds = sizeof(double) * (size_t)sx_slots(o->n) * kSxLanes;
-    auto* kern = &k_simplex_batch<KIND>;
-    if (lds > 64 * 1024)
-        PNOL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
-    const size_t blocks = (nstart + kSxLanes - 1) / kSxLanes;
-    ScopedTimer tm(ctx, "simplex_batch");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kSxLanes), lds, ctx->stream, o->n, nstart,
-                       (const double*)o->p0, (const double*)o->p1, o->power, prm[0], prm[1], prm[2], prm[3],
-                       (int)prm[4], prm[5], prm[6], seed, X, f0, fopt, iters, evals);
-    return launch_check();
-}
-
 }  // namespace
 
 int launch_simplex_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, unsigned long long seed,
                          long long nstart, double* X, double* f0, double* fopt, int* iters, long long* evals) {
-    if (!ctx || !o || !params || !X || !f0 || !fopt || !iters || !evals || nstart <= 0) return PNOL_ERR_ARG;
-    if (o->n < 1) return PNOL_ERR_ARG;
-    if (o->n > PNOL_SIMPLEX_BATCH_NMAX) return PNOL_ERR_UNSUPPORTED;
-    if (((size_t)nstart + kSxLanes - 1) / kSxLanes > 0x7fffffffull) return PNOL_ERR_ARG;
-    if (o->kind == PNOL_OBJ_QUADRATIC && (o->len0 < (size_t)o->n || o->len1 < (size_t)o->n)) return PNOL_ERR_ARG;
-    switch (o->kind) {
-        case PNOL_OBJ_ROSENBROCK:
-            return sx_launch<PNOL_OBJ_ROSENBROCK>(ctx, o, params, seed, (size_t)nstart, X, f0, fopt, iters, evals);
-        case PNOL_OBJ_POWER:
-            return sx_launch<PNOL_OBJ_POWER>(ctx, o, params, seed, (size_t)nstart, X, f0, fopt, iters, evals);
-        case PNOL_OBJ_QUADRATIC:
-            return sx_launch<PNOL_OBJ_QUADRATIC>(ctx, o, params, seed, (size_t)nstart, X, f0, fopt, iters, evals);
-        default:
-            return PNOL_ERR_UNSUPPORTED;
-    }
+    if (!ctx || !params || !X || !f0 || !fopt || !iters || !evals || nstart <= 0) return PNOL_ERR_ARG;
+    PNOL_CHECK(scalar_batch_check(o, PNOL_SIMPLEX_BATCH_NMAX));
+    const double* p = params;
+    const size_t ns = (size_t)nstart, lds = sizeof(double) * (size_t)sx_slots(o->n) * kLaneBatchLanes;
+    return scalar_batch_dispatch(o->kind, [&](auto kind) {
+        return lane_batch_launch(ctx, "simplex_batch", &k_simplex_batch<decltype(kind)::value>, ns, lds, o->n, ns,
+                                 (const double*)o->p0, (const double*)o->p1, o->power, p[0], p[1], p[2], p[3],
+                                 (int)p[4], p[5], p[6], seed, X, f0, fopt, iters, evals);
+    });
 }
 
 }  // namespace pnol

@@ -363,13 +363,9 @@ int launch_synthetic_quadratic(pnol_ctx* ctx, unsigned long long seed, int n, do
 int launch_synthetic_linres(pnol_ctx* ctx, unsigned long long seed, int m, int n, double* A, double* xstar,
                             double* y);
 int launch_fill(pnol_ctx* ctx, double* p, size_t count, double value);
-// Every problem's whole LevMarq::findMin in one launch, one lane per problem (lm_batch.hip).
-// params: host, LevMarq::setParams order; X: x0 in, optimum out; F0 / FOpt nullable
-int launch_lm_batch(pnol_ctx* ctx, const pnol_lm_batch* b, const double* y, const double* params, double* X,
-                    double* chi0, double* chi, int* iters, long long* evals, double* F0, double* FOpt);
-// nstart independent SimplexSearch::findMin runs of one scalar objective in one launch, one lane
-// per start (simplex_batch.hip).  params: host, setSimplexParams order (maxIter already checked);
-// start s draws from the stream seeded seed + s; X: the starts in, the optima out
+
+// ---- the batched solvers: one lane per problem, the whole algorithm in one launch (what the
+// three kernel files share: kernels/lane_batch.hpp)
 // the 8 setSimplexParams values of the C ABI: maxIter (a double there, cast to int) must be a
 // non-negative int; nothing here touches a device
 inline int simplex_check_params(const double* p) {
@@ -377,8 +373,6 @@ inline int simplex_check_params(const double* p) {
     if (!(p[4] >= 0.0 && p[4] <= 2147483647.0)) return PNOL_ERR_ARG;
     return PNOL_OK;
 }
-int launch_simplex_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, unsigned long long seed,
-                         long long nstart, double* X, double* f0, double* fopt, int* iters, long long* evals);
 // the 12 BFGS::setParams values of the batched C ABI: maxIterLineSearch and maxIter (doubles
 // there, cast to int) must be non-negative ints, and the FD initial Hessian is not offered;
 // nothing here touches a device
@@ -388,6 +382,15 @@ inline int bfgs_batch_check_params(const double* p) {
     if (p[10] != 0.0) return PNOL_ERR_UNSUPPORTED;
     return PNOL_OK;
 }
+// Every problem's whole LevMarq::findMin in one launch, one lane per problem (lm_batch.hip).
+// params: host, LevMarq::setParams order; X: x0 in, optimum out; F0 / FOpt nullable
+int launch_lm_batch(pnol_ctx* ctx, const pnol_lm_batch* b, const double* y, const double* params, double* X,
+                    double* chi0, double* chi, int* iters, long long* evals, double* F0, double* FOpt);
+// nstart independent SimplexSearch::findMin runs of one scalar objective in one launch, one lane
+// per start (simplex_batch.hip).  params: host, setSimplexParams order (maxIter already checked);
+// start s draws from the stream seeded seed + s; X: the starts in, the optima out
+int launch_simplex_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, unsigned long long seed,
+                         long long nstart, double* X, double* f0, double* fopt, int* iters, long long* evals);
 // nstart independent BFGS::findMin runs of one scalar objective in one launch, one lane per start
 // (bfgs_batch.hip).  params: host, BFGS::setParams order (already checked); X: the starts in, the
 // optima out

@@ -494,18 +494,25 @@ def host_run_simplex(fn, x0, params, seed):
     return X, res
 
 
-def run_simplex_batch(obj, x0, params, seed, kind=None, power=2.0, p0=None, p1=None):
-    """Batched SimplexSearch: the nstart rows of x0 (nstart x n) are independent searches of one
-    scalar objective in one launch, start s on the stream seeded seed + s; params =
-    setSimplexParams (8 values).  obj: a DeviceObjective (solved on its context through
-    pnol_simplex_batch_solve_d), or None for the process default context through the host-pointer
-    entry point pnol_run_simplex_batch, the objective then given by kind / power / p0 / p1.
-    Returns (X, f0, fopt, iters, evals) as numpy arrays."""
+def _bfgs_batch_params(params):
+    p = np.array(params, dtype=np.float64)
+    if p.size != 12:
+        raise ValueError("params: the 12 values of BFGS::setParams")
+    return p
+
+
+def _run_scalar_batch(name, nf, to_params, obj, x0, params, extra, kind, power, p0, p1):
+    """The shared body of run_simplex_batch / run_bfgs_batch: pnol_<name>_batch_solve_d on obj's
+    context, or pnol_run_<name>_batch on host arrays when obj is None.  nf: the per-start double
+    outputs (f0, fopt[, gnorm]); to_params: checks params and returns them as an array; extra: the
+    arguments between params and the sizes / X (the simplex's seed).  Returns (X, the nf arrays,
+    iters, evals) as one tuple."""
     X = np.ascontiguousarray(np.array(x0, dtype=np.float64))
     if X.ndim != 2:
         raise ValueError("x0 must be nstart x n")
     nstart, n = int(X.shape[0]), int(X.shape[1])
-    p = _simplex_params(params)
+    p = to_params(params)
+    cap = max(nstart, 1)
     if obj is not None:
         if n != obj.n:
             raise ValueError("x0 rows must have the objective's n values")
@@ -513,24 +520,36 @@ def run_simplex_batch(obj, x0, params, seed, kind=None, power=2.0, p0=None, p1=N
         t = ctx.torch
         dev = f"cuda:{ctx.device}"
         Xd = ctx.tensor(X)
-        f0, fo = ctx.empty(max(nstart, 1)), ctx.empty(max(nstart, 1))
-        iters = t.empty(max(nstart, 1), dtype=t.int32, device=dev)
-        evals = t.empty(max(nstart, 1), dtype=t.int64, device=dev)
-        L.check(L.lib().pnol_simplex_batch_solve_d(ctx.h, obj.h, _dptr(p), seed, nstart, _ptr(Xd), _ptr(f0), _ptr(fo),
-                                                   _ptr(iters), _ptr(evals)), "pnol_simplex_batch_solve_d")
+        fs = [ctx.empty(cap) for _ in range(nf)]
+        iters = t.empty(cap, dtype=t.int32, device=dev)
+        evals = t.empty(cap, dtype=t.int64, device=dev)
+        entry = f"pnol_{name}_batch_solve_d"
+        L.check(getattr(L.lib(), entry)(ctx.h, obj.h, _dptr(p), *extra, nstart, _ptr(Xd), *[_ptr(f) for f in fs],
+                                        _ptr(iters), _ptr(evals)), entry)
         ctx.synchronize()
-        return tuple(a.cpu().numpy() for a in (Xd, f0, fo, iters, evals))
+        return tuple(a.cpu().numpy() for a in (Xd, *fs, iters, evals))
     a0 = None if p0 is None else np.ascontiguousarray(p0, dtype=np.float64).ravel()
     a1 = None if p1 is None else np.ascontiguousarray(p1, dtype=np.float64).ravel()
-    f0, fo = np.zeros(max(nstart, 1)), np.zeros(max(nstart, 1))
-    iters, evals = np.zeros(max(nstart, 1), dtype=np.int32), np.zeros(max(nstart, 1), dtype=np.int64)
+    fs = [np.zeros(cap) for _ in range(nf)]
+    iters, evals = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int64)
     Xh = X if X.size else np.zeros(1)
-    L.check(L.lib().pnol_run_simplex_batch(kind, n, C.c_double(power), _dptr(a0) if a0 is not None else None,
-                                           0 if a0 is None else a0.size, _dptr(a1) if a1 is not None else None,
-                                           0 if a1 is None else a1.size, nstart, _dptr(p), seed, _dptr(Xh), _dptr(f0),
-                                           _dptr(fo), iters.ctypes.data_as(C.POINTER(C.c_int)),
-                                           evals.ctypes.data_as(C.POINTER(C.c_longlong))), "pnol_run_simplex_batch")
-    return X, f0[:nstart], fo[:nstart], iters[:nstart], evals[:nstart]
+    entry = f"pnol_run_{name}_batch"
+    L.check(getattr(L.lib(), entry)(kind, n, C.c_double(power), _dptr(a0) if a0 is not None else None,
+                                    0 if a0 is None else a0.size, _dptr(a1) if a1 is not None else None,
+                                    0 if a1 is None else a1.size, nstart, _dptr(p), *extra, _dptr(Xh),
+                                    *[_dptr(f) for f in fs], iters.ctypes.data_as(C.POINTER(C.c_int)),
+                                    evals.ctypes.data_as(C.POINTER(C.c_longlong))), entry)
+    return (X, *[f[:nstart] for f in fs], iters[:nstart], evals[:nstart])
+
+
+def run_simplex_batch(obj, x0, params, seed, kind=None, power=2.0, p0=None, p1=None):
+    """Batched SimplexSearch: the nstart rows of x0 (nstart x n) are independent searches of one
+    scalar objective in one launch, start s on the stream seeded seed + s; params =
+    setSimplexParams (8 values).  obj: a DeviceObjective (solved on its context through
+    pnol_simplex_batch_solve_d), or None for the process default context through the host-pointer
+    entry point pnol_run_simplex_batch, the objective then given by kind / power / p0 / p1.
+    Returns (X, f0, fopt, iters, evals) as numpy arrays."""
+    return _run_scalar_batch("simplex", 2, _simplex_params, obj, x0, params, (seed,), kind, power, p0, p1)
 
 
 def run_bfgs_batch(obj, x0, params, kind=None, power=2.0, p0=None, p1=None):
@@ -540,38 +559,7 @@ def run_bfgs_batch(obj, x0, params, kind=None, power=2.0, p0=None, p1=None):
     the process default context through the host-pointer entry point pnol_run_bfgs_batch, the
     objective then given by kind / power / p0 / p1.  Returns (X, f0, fopt, gnorm, iters, evals) as
     numpy arrays; gnorm is the loop's last gradient norm."""
-    X = np.ascontiguousarray(np.array(x0, dtype=np.float64))
-    if X.ndim != 2:
-        raise ValueError("x0 must be nstart x n")
-    nstart, n = int(X.shape[0]), int(X.shape[1])
-    p = np.array(params, dtype=np.float64)
-    if p.size != 12:
-        raise ValueError("params: the 12 values of BFGS::setParams")
-    if obj is not None:
-        if n != obj.n:
-            raise ValueError("x0 rows must have the objective's n values")
-        ctx = obj.ctx
-        t = ctx.torch
-        dev = f"cuda:{ctx.device}"
-        Xd = ctx.tensor(X)
-        f0, fo, gn = ctx.empty(max(nstart, 1)), ctx.empty(max(nstart, 1)), ctx.empty(max(nstart, 1))
-        iters = t.empty(max(nstart, 1), dtype=t.int32, device=dev)
-        evals = t.empty(max(nstart, 1), dtype=t.int64, device=dev)
-        L.check(L.lib().pnol_bfgs_batch_solve_d(ctx.h, obj.h, _dptr(p), nstart, _ptr(Xd), _ptr(f0), _ptr(fo), _ptr(gn),
-                                                _ptr(iters), _ptr(evals)), "pnol_bfgs_batch_solve_d")
-        ctx.synchronize()
-        return tuple(a.cpu().numpy() for a in (Xd, f0, fo, gn, iters, evals))
-    a0 = None if p0 is None else np.ascontiguousarray(p0, dtype=np.float64).ravel()
-    a1 = None if p1 is None else np.ascontiguousarray(p1, dtype=np.float64).ravel()
-    f0, fo, gn = np.zeros(max(nstart, 1)), np.zeros(max(nstart, 1)), np.zeros(max(nstart, 1))
-    iters, evals = np.zeros(max(nstart, 1), dtype=np.int32), np.zeros(max(nstart, 1), dtype=np.int64)
-    Xh = X if X.size else np.zeros(1)
-    L.check(L.lib().pnol_run_bfgs_batch(kind, n, C.c_double(power), _dptr(a0) if a0 is not None else None,
-                                        0 if a0 is None else a0.size, _dptr(a1) if a1 is not None else None,
-                                        0 if a1 is None else a1.size, nstart, _dptr(p), _dptr(Xh), _dptr(f0),
-                                        _dptr(fo), _dptr(gn), iters.ctypes.data_as(C.POINTER(C.c_int)),
-                                        evals.ctypes.data_as(C.POINTER(C.c_longlong))), "pnol_run_bfgs_batch")
-    return X, f0[:nstart], fo[:nstart], gn[:nstart], iters[:nstart], evals[:nstart]
+    return _run_scalar_batch("bfgs", 3, _bfgs_batch_params, obj, x0, params, (), kind, power, p0, p1)
 
 
 def run_levmarq(obj: DeviceObjective, x0, params, which=0, host_eval=False):

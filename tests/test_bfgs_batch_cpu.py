@@ -140,6 +140,20 @@ def test_short_quadratic_data_is_refused():
     assert _batch(L.OBJ_QUADRATIC, 5, 8, len1=4) == L.PNOL_ERR_ARG
 
 
+def test_refusal_precedence():
+    """The order the refusals are applied in: the parameters' ranges, then the unsupported option,
+    then the kind, then non-positive sizes, then the NMAX limit, then the quadratic's data and the
+    output pointers."""
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    assert _batch(L.OBJ_LINRES, 3, 8, BR.params(maxIter=-1)) == L.PNOL_ERR_ARG           # parameters before kind
+    assert _batch(L.OBJ_LINRES, 0, 8) == L.PNOL_ERR_UNSUPPORTED                          # kind before sizes
+    assert _batch(L.OBJ_ROSENBROCK, L.BFGS_BATCH_NMAX + 1, 0) == L.PNOL_ERR_ARG          # sizes before NMAX
+    assert _batch(L.OBJ_QUADRATIC, 5, 8, len0=4, null="fopt") == L.PNOL_ERR_ARG
+    # the range check before the unsupported-option check
+    assert _batch(L.OBJ_ROSENBROCK, 3, 8, BR.params(initHessFD=1, maxIter=-1)) == L.PNOL_ERR_ARG
+    assert _batch(L.OBJ_LINRES, 3, 8, BR.params(initHessFD=1)) == L.PNOL_ERR_UNSUPPORTED
+
+
 def test_no_device_is_reported_on_a_cpu_host():
     from parallelnonlinearoptimizationlibrary_amd import _lib as L
     if L.device_count() > 0:

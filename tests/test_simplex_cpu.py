@@ -129,7 +129,7 @@ def test_simplex_diff_on_a_hand_made_simplex():
 
 
 # ---- argument checks: before any device use, so the same with or without a GPU ------------
-def _batch(kind, n, nstart, params=SR.DEFAULTS):
+def _batch(kind, n, nstart, params=SR.DEFAULTS, len0=None, len1=None, null=None):
     from parallelnonlinearoptimizationlibrary_amd import _lib as L
     ns, nn = max(nstart, 1), max(n, 1)
     X = np.full(ns * nn, 3.0)
@@ -138,9 +138,13 @@ def _batch(kind, n, nstart, params=SR.DEFAULTS):
     p = np.array(params, dtype=np.float64)
     d = np.ones(nn)
     dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-    return L.lib().pnol_run_simplex_batch(kind, n, 2.0, dp(d), d.size, dp(d), d.size, nstart, dp(p), SR.SEED0, dp(X),
-                                          dp(f0), dp(fo), iters.ctypes.data_as(C.POINTER(C.c_int)),
-                                          evals.ctypes.data_as(C.POINTER(C.c_longlong)))
+    args = {"p": dp(p), "X": dp(X), "f0": dp(f0), "fopt": dp(fo),
+            "iters": iters.ctypes.data_as(C.POINTER(C.c_int)), "evals": evals.ctypes.data_as(C.POINTER(C.c_longlong))}
+    if null:
+        args[null] = None
+    return L.lib().pnol_run_simplex_batch(kind, n, 2.0, dp(d), d.size if len0 is None else len0, dp(d),
+                                          d.size if len1 is None else len1, nstart, args["p"], SR.SEED0, args["X"],
+                                          args["f0"], args["fopt"], args["iters"], args["evals"])
 
 
 def _host_status(params):
@@ -174,6 +178,30 @@ def test_other_kinds_are_unsupported():
     from parallelnonlinearoptimizationlibrary_amd import _lib as L
     assert _batch(L.OBJ_LINRES, 3, 8) == L.PNOL_ERR_UNSUPPORTED
     assert _batch(L.OBJ_CUBIC, 4, 8) == L.PNOL_ERR_UNSUPPORTED
+
+
+def test_null_pointers_are_refused():
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    for null in ("p", "X", "f0", "fopt", "iters", "evals"):
+        assert _batch(L.OBJ_ROSENBROCK, 3, 8, null=null) == L.PNOL_ERR_ARG, null
+    # the device-pointer entry point without a context or an objective
+    assert L.lib().pnol_simplex_batch_solve_d(None, None, None, 1, 8, None, None, None, None, None) == L.PNOL_ERR_ARG
+
+
+def test_short_quadratic_data_is_refused():
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    assert _batch(L.OBJ_QUADRATIC, 5, 8, len0=4) == L.PNOL_ERR_ARG
+    assert _batch(L.OBJ_QUADRATIC, 5, 8, len1=4) == L.PNOL_ERR_ARG
+
+
+def test_refusal_precedence():
+    """The order the refusals are applied in: parameters, then the kind, then non-positive sizes,
+    then the NMAX limit, then the quadratic's data and the output pointers."""
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    assert _batch(L.OBJ_LINRES, 3, 8, SR.params(maxIter=-1)) == L.PNOL_ERR_ARG           # parameters before kind
+    assert _batch(L.OBJ_LINRES, 0, 8) == L.PNOL_ERR_UNSUPPORTED                          # kind before sizes
+    assert _batch(L.OBJ_ROSENBROCK, L.SIMPLEX_BATCH_NMAX + 1, 0) == L.PNOL_ERR_ARG       # sizes before NMAX
+    assert _batch(L.OBJ_QUADRATIC, 5, 8, len0=4, null="fopt") == L.PNOL_ERR_ARG
 
 
 def test_no_device_is_reported_on_a_cpu_host():
