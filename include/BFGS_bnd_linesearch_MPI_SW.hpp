@@ -54,6 +54,7 @@ class BFGS_Bnd_MPI_SW : public AlgorithmBnd {
     int recurFlag;
     int poolSize = 0;    // 0: Nprocs = number of ranks (reference behaviour)
     int updateMode = 0;
+    struct Policy;       // this class's side of the active-set recursion (library internal)
 
   public:
     void findMinBnd(vector<double>& X, vector<double>& Xlb, vector<double>& Xub, double& f0, double& fOpt);

@@ -6,21 +6,9 @@
 #include <iostream>
 
 #include "BFGS_with_linesearch.hpp"
-#include "dense_hessian.hpp"
-#include "line_points.hpp"
+#include "bfgs_common.hpp"
 
 using namespace pnol;
-
-namespace {
-
-double sign_of(double x) { return x > 0 ? 1.0 : (x < 0 ? -1.0 : 0.0); }
-
-void print_vec(const std::vector<double>& v) {
-    for (double x : v) std::printf("%.17g ", x);
-    std::printf("\n");
-}
-
-}  // namespace
 
 double cubicInterpMin(double alo, double ahi, double plo, double phi, double dlo, double dhi, vector<double>& X,
                       vector<double>& p) {
@@ -45,14 +33,14 @@ void updateHessianInv(vector<vector<double>>& D, vector<double>& g, vector<doubl
 }
 
 double BFGS::lineSearchObj(double alpha, vector<double>& X, vector<double>& p) {
-    std::vector<double> Xa(X.size());
-    for (size_t i = 0; i < X.size(); ++i) Xa[i] = X[i] + alpha * p[i];
+    std::vector<double> Xa;
+    line_point(X, p, alpha, Xa);
     return objPtr->objEval(Xa);
 }
 
 double BFGS::lineSearchFDDerivative(double alpha, double phialpha, vector<double>& X, vector<double>& p) {
-    std::vector<double> Xa(X.size());
-    for (size_t i = 0; i < X.size(); ++i) Xa[i] = X[i] + (alpha + dalpha) * p[i];
+    std::vector<double> Xa;
+    line_point(X, p, alpha + dalpha, Xa);
     const double Fa = objPtr->objEval(Xa);
     return (Fa - phialpha) / dalpha;
 }
@@ -121,68 +109,27 @@ void BFGS::cubicInterpolationLineSearch(vector<double>& X, double FX, vector<dou
 
 void BFGS::findMin(vector<double>& X, double& f0, double& fOpt) {
     // BFGS_with_linesearch.cpp:12-139
-    const int n = (int)X.size();
     PhaseClock total(prof_slot(profile, kProfTotal));
-    pnol_ctx* ctx = require_ctx();
-    DenseInverseHessian D(ctx, n, updateMode);
-    if (initHessFD) init_from_fd_hessian(objPtr, X, dXHess, D);
-    else D.setIdentity();
-
-    std::vector<double> dX(n, dXGrad), dFdX(n), dFdXprev(n), p(n), pnext(n), s(n), y(n), Xprev(n);
-    {
-        PhaseClock t(prof_slot(profile, kProfGrad));
-        objPtr->gradientApproximation(X, dX, dFdX);
-        if (profile) profile[kProfGradCalls] += 1;
-    }
-    double F = objPtr->objEval(X);
-    f0 = F;
-    int iter = 0;
-    double xdiff = xMinDiff * 2, gnorm = 2 * minGrad2Norm;
-    bool have_next = false;
-    while (iter < maxIter && xdiff > xMinDiff && gnorm > minGrad2Norm) {
-        dFdXprev = dFdX;
-        if (have_next) {
-            p = pnext;
-        } else {
-            PhaseClock t(prof_slot(profile, kProfUpdate));
-            D.direction(dFdX, p);
-        }
-        double alpha = 0, Fopt = 0;
-        {
-            PhaseClock t(prof_slot(profile, kProfLineSearch));
-            cubicInterpolationLineSearch(X, F, dFdX, p, alpha, Fopt);
-        }
-        for (int i = 0; i < n; ++i) { Xprev[i] = X[i]; X[i] = X[i] + alpha * p[i]; }
-        F = Fopt;
-        {
-            PhaseClock t(prof_slot(profile, kProfGrad));
-            objPtr->gradientApproximation(X, dX, dFdX);
-            if (profile) profile[kProfGradCalls] += 1;
-        }
-        for (int i = 0; i < n; ++i) { s[i] = alpha * p[i]; y[i] = dFdX[i] - dFdXprev[i]; }
-        {
-            PhaseClock t(prof_slot(profile, kProfUpdate));
-            D.update(y, s, &dFdX, &pnext);
-        }
-        have_next = true;
-        xdiff = 0;
-        for (int i = 0; i < n; ++i) xdiff += std::fabs(X[i] - Xprev[i]);
-        gnorm = std::sqrt(seq_dot(dFdX, dFdX));
-        if (verbose) {
+    const QuasiNewtonParams q{dXGrad, dXHess, xMinDiff, minGrad2Norm, maxIter, updateMode, initHessFD, false, profile};
+    quasi_newton_loop(
+        q, objPtr, X, f0, fOpt,
+        [&](vector<double>& x, vector<double>& dX, vector<double>& g) { objPtr->gradientApproximation(x, dX, g); },
+        [&](vector<double>& x, double F, vector<double>& g, vector<double>& p, double& alpha, double& Fopt) {
+            cubicInterpolationLineSearch(x, F, g, p, alpha, Fopt);
+        },
+        [&](int iter, double xdiff, double gnorm, double F) {
+            if (!verbose) return;
             std::cout << "At iter = " << iter << " the mean abs xdiff is " << xdiff << " and the grad2norm = " << gnorm
                       << std::endl;
             std::cout << " with a minimum function evaluation of " << F << std::endl;
-        }
-        iter = iter + 1;
-    }
-    if (profile) profile[kProfIters] = iter;
-    fOpt = F;
-    if (verbose) {
-        std::cout << std::endl << "-----------------------------------------------------------------------------------" << std::endl;
-        std::cout << "Completed bfgs." << std::endl;
-        std::cout << "f0 = " << f0 << ", fOpt = " << fOpt << " with variable:" << std::endl;
-        std::cout << "X = ";
-        print_vec(X);
-        std::cout << "-----------------------------------------------------------------------------------" << std::endl << std::endl;
-    }
+        },
+        [&](double f0v, double fOptv, const vector<double>& x) {
+            if (!verbose) return;
+            std::cout << std::endl << "-----------------------------------------------------------------------------------" << std::endl;
+            std::cout << "Completed bfgs." << std::endl;
+            std::cout << "f0 = " << f0v << ", fOpt = " << fOptv << " with variable:" << std::endl;
+            std::cout << "X = ";
+            print_vec(x);
+            std::cout << "-----------------------------------------------------------------------------------" << std::endl << std::endl;
+        });
 }

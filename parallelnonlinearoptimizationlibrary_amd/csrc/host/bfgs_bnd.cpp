@@ -7,53 +7,11 @@
 #include <cstdlib>
 #include <iostream>
 
-#include "../pnol_comm.hpp"
 #include "BFGS_bnd_linesearch.hpp"
+#include "bfgs_common.hpp"
 #include "deep_stack.hpp"
-#include "dense_hessian.hpp"
-#include "line_points.hpp"
-#include "recur_simd.hpp"
 
 using namespace pnol;
-
-namespace {
-double sign_of(double x) { return x > 0 ? 1.0 : (x < 0 ? -1.0 : 0.0); }
-// PNOL_BND_DETAIL=1: where the host time of the "other" phase goes (diagnostics, stderr)
-enum { kDetFreeze, kDetGather, kDetCopyBack, kDetIterLoops, kDetCount };
-thread_local double g_det[kDetCount];
-double* det_slot(int k) {
-    static const bool on = [] {
-        const char* e = std::getenv("PNOL_BND_DETAIL");
-        return e && std::atoi(e) != 0;
-    }();
-    return on ? &g_det[k] : nullptr;
-}
-// drop positions fk (ascending) of v[0, n): the kept entries slide down run by run
-template <class T>
-void drop_positions(std::vector<T>& v, const std::vector<int>& fk, int n) {
-    if (fk.empty()) return;
-    int dst = fk[0];
-    for (size_t f = 0; f < fk.size(); ++f) {
-        const int b = fk[f] + 1, e = f + 1 < fk.size() ? fk[f + 1] : n;
-        std::copy(v.begin() + b, v.begin() + e, v.begin() + dst);
-        dst += e - b;
-    }
-}
-// the inverse: reopen the gaps at positions fk of v[0, n) (their contents are the caller's)
-template <class T>
-void reopen_positions(std::vector<T>& v, const std::vector<int>& fk, int n) {
-    int hi = n;
-    for (int f = (int)fk.size() - 1; f >= 0; --f) {
-        const int b = fk[f] + 1;
-        std::copy_backward(v.begin() + (b - f - 1), v.begin() + (hi - f - 1), v.begin() + hi);
-        hi = fk[f];
-    }
-}
-void print_vec(const std::vector<double>& v) {
-    for (double x : v) std::printf("%.17g ", x);
-    std::printf("\n");
-}
-}  // namespace
 
 void checkBoxBounds(std::vector<double>& X, std::vector<double>& Xlb, std::vector<double>& Xub) {
     for (size_t i = 0; i < X.size(); ++i) {
@@ -86,15 +44,15 @@ double cubicInterpMinSimple(double aa, double ab, double pa, double pb, double d
 
 double BFGS_Bnd::lineSearchObj(double alpha, vector<double>& X, vector<double>& p, vector<double>& cX,
                                vector<bool>& cI) {
-    std::vector<double> Xa(X.size());
-    for (size_t i = 0; i < X.size(); ++i) Xa[i] = X[i] + alpha * p[i];
+    std::vector<double> Xa;
+    line_point(X, p, alpha, Xa);
     return objPtr->objEvalRecur(Xa, cX, cI);
 }
 
 double BFGS_Bnd::lineSearchFDDerivative(double alpha, double phialpha, vector<double>& X, vector<double>& p,
                                         vector<double>& cX, vector<bool>& cI) {
-    std::vector<double> Xa(X.size());
-    for (size_t i = 0; i < X.size(); ++i) Xa[i] = X[i] + (alpha + dalpha) * p[i];
+    std::vector<double> Xa;
+    line_point(X, p, alpha + dalpha, Xa);
     const double Fa = objPtr->objEvalRecur(Xa, cX, cI);
     return (Fa - phialpha) / dalpha;
 }
@@ -186,258 +144,62 @@ void BFGS_Bnd::cubicInterpolationLineSearchBnd(vector<double>& X, vector<double>
     }
 }
 
+// BFGS_Bnd's side of the shared active-set recursion (bfgs_common.hpp): the serial Recur
+// gradient, the Wolfe search above, D on one GPU with the next direction out of the update's pass
+struct BFGS_Bnd::Policy {
+    static constexpr bool kShardD = false, kFusedDirection = true, kDetailClocks = true;
+    static constexpr int kStepTextAbove = 1, kRecursedTextAbove = 0;
+    BFGS_Bnd& b;
+    void gradient(vector<double>& X, vector<double>& dX, vector<double>& dFdX, vector<double>& cX, vector<bool>& cI) {
+        b.objPtr->gradientApproximationRecur(X, dX, dFdX, cX, cI);
+    }
+    void lineSearch(vector<double>& X, vector<double>& Xlb, vector<double>& Xub, double F, vector<double>& dFdX,
+                    vector<double>& p, vector<double>& cX, vector<bool>& cI, double& alpha, double& Fopt) {
+        b.cubicInterpolationLineSearchBnd(X, Xlb, Xub, F, dFdX, p, cX, cI, alpha, Fopt);
+    }
+    const char* startText() const { return "  Starting bounded BFGS with line search. "; }
+    bool announcesBoundary(int verbose) const { return verbose != 0; }
+    void boundaryText(size_t nfrozen, const vector<double>&, double) const {
+        std::cout << std::endl << "Optimizer reached box boundary; steepest descent points outside the box at "
+                  << nfrozen << " coordinate(s); recursing on the remaining ones." << std::endl;
+    }
+    BndParams params() const {
+        return BndParams{b.bndTol, b.dXGrad, b.dXHess, b.xMinDiff, b.minGrad2Norm, b.maxIter, b.updateMode, b.verbose,
+                         b.initHessFD, &b.dXGradVec, &b.initialScalingVec, b.fTrace, b.profile};
+    }
+};
+
 void BFGS_Bnd::boundaryAssessment(double& F, vector<double>& X, vector<double>& p, vector<double>& dFdX,
                                   DenseInverseHessian& D, vector<double>& Xlb, vector<double>& Xub, vector<double>& dX,
                                   vector<double>& cX, vector<bool>& cI, bool& optimFlag, int& recurFlag) {
     // BFGS_bnd_linesearch.cpp:503-728
-    const int ncur = (int)X.size();
-    const int Ndim = (int)cX.size();
-    PhaseClock tf(det_slot(kDetFreeze));
-    std::vector<int> fk, fi;   // positions in X frozen by this assessment (ascending), their full indices
-    bool bndFlag = false;
-    int Nconst = 0;            // coordinates frozen after the tests
-    if (freeIdxLive && (int)freeIdx.size() == ncur) {
-        // the level's coordinates are the free ones of cI in order (freeIdx): the reference's
-        // walk over all Ndim indicators reduces to the tests over X's own positions
-        recur::bound_hits(X.data(), Xlb.data(), Xub.data(), p.data(), dFdX.data(), (size_t)ncur, bndTol, fk);
-        for (int k : fk) {
-            const int i = freeIdx[k];
-            cI[i] = true; cX[i] = X[k]; fi.push_back(i);
-        }
-        bndFlag = !fk.empty();
-        Nconst = Ndim - ncur + (int)fk.size();
-    } else {
-        // any constantIndicator: the reference's walk, evaluated without short-circuit
-        // branches (only a coordinate that hits a bound takes one)
-        freeIdxLive = false;
-        const int klast = ncur > 0 ? ncur - 1 : 0;
-        int icur = 0;
-        for (int i = 0; i < Ndim; ++i) {
-            const bool c = cI[i];
-            Nconst += c;
-            if (ncur == 0) continue;
-            const int k = icur < klast ? icur : klast;
-            const double xk = X[k], pk = p[k], gk = dFdX[k];
-            const bool lo = (std::fabs(xk - Xlb[k]) < bndTol) & ((pk < 0) | (gk > 0));
-            const bool hi = (std::fabs(xk - Xub[k]) < bndTol) & ((pk > 0) | (gk < 0));
-            if (!c & (lo | hi)) {
-                bndFlag = true; cI[i] = true; cX[i] = xk; fi.push_back(i);
-                if (icur < ncur) fk.push_back(icur);
-            }
-            icur += !c;
-        }
-        Nconst += (int)fi.size();   // == the count of cI after the freezes
-    }
-    if (bndFlag && verbose && comm_rank() == ROOT_ID) {
-        std::cout << std::endl << "Optimizer reached box boundary; steepest descent points outside the box at "
-                  << fi.size() << " coordinate(s); recursing on the remaining ones." << std::endl;
-    }
-    const int nr = Ndim - Nconst;
-    tf.stop();
-    if (bndFlag && nr > 0) {
-        PhaseClock tg(det_slot(kDetGather));
-        // The reduced problem runs on these same vectors: the frozen entries are set aside and
-        // the others slide down in place (the reference gathers them into fresh vectors at every
-        // level), so one set of n-vectors serves the whole recursion -- about 11k levels at
-        // n = 16384 -- instead of five new ones per level.
-        const int nf = (int)fk.size(), nk = ncur - nf;
-        std::vector<double> held((size_t)nf * 5);
-        for (int f = 0; f < nf; ++f) {
-            const int k = fk[f];
-            double* h = &held[(size_t)f * 5];
-            h[0] = X[k]; h[1] = dFdX[k]; h[2] = Xlb[k]; h[3] = Xub[k]; h[4] = dX[k];
-        }
-        const bool idx = freeIdxLive;
-        for (vector<double>* v : {&X, &dFdX, &Xlb, &Xub, &dX}) {
-            drop_positions(*v, fk, ncur);
-            v->resize(nr);
-            // the fallback walk (freeIdxLive off, e.g. below a level that froze every coordinate)
-            // can leave nr != nk: entries past the nk kept ones read 0.0, as the reference's
-            // fresh XR(nr) would hold them (never stale values from the compaction)
-            if (nr > nk) std::fill(v->begin() + nk, v->end(), 0.0);
-        }
-        if (idx) {
-            drop_positions(freeIdx, fk, ncur);
-            freeIdx.resize(nr);
-        }
-        const double FR = F;
-        double Fr = F;
-        // the outer D is discarded while the reduced problem runs (reset below), so the
-        // reduced D takes over its device buffer: one n x n matrix for the whole recursion
-        DenseInverseHessian DR(D, nr, updateMode);
-        if (!initialScalingVec.empty()) {
-            std::vector<double> scaleR;
-            if (idx) {
-                scaleR.resize(nr);
-                for (int k = 0; k < nr; ++k) scaleR[k] = initialScalingVec[freeIdx[k]];
-            } else {
-                for (int i = 0; i < Ndim; ++i) if (!cI[i]) scaleR.push_back(initialScalingVec[i]);
-            }
-            DR.setIdentity(&scaleR);
-        } else {
-            DR.setIdentity();
-        }
-        recurFlag = true;
-        // the caller's direction (and the next one its update prepared) are recomputed after
-        // the recursion: release them while it runs
-        std::vector<double>().swap(p);
-        if (pnextHeld) std::vector<double>().swap(*pnextHeld);
-        pnextHeld = nullptr;
-        tg.stop();
-        ++depth;
-        if (profile && depth > profile[kProfDepth]) profile[kProfDepth] = depth;
-        mainBFGSLoop(Fr, X, dFdX, DR, Xlb, Xub, dX, cX, cI, optimFlag, recurFlag);
-        --depth;
-        assessRecursed = true;   // after the reduced loop, which clears it for its own levels
-        PhaseClock tc(det_slot(kDetCopyBack));
-        F = nk > 0 ? Fr : FR;
-        for (vector<double>* v : {&X, &dFdX, &Xlb, &Xub, &dX}) {
-            v->resize(ncur);
-            reopen_positions(*v, fk, ncur);
-        }
-        for (int f = 0; f < nf; ++f) {
-            const int k = fk[f];
-            const double* h = &held[(size_t)f * 5];
-            X[k] = h[0]; dFdX[k] = h[1]; Xlb[k] = h[2]; Xub[k] = h[3]; dX[k] = h[4];
-        }
-        if (idx && freeIdxLive) {   // (a level below may have dropped the index map)
-            freeIdx.resize(ncur);
-            reopen_positions(freeIdx, fk, ncur);
-            for (int f = 0; f < nf; ++f) freeIdx[fk[f]] = fi[f];
-        }
-        for (int i : fi) cI[i] = false;
-        if (!initialScalingVec.empty()) {
-            std::vector<double> scale;
-            if (freeIdxLive) {
-                scale.resize(ncur);
-                for (int k = 0; k < ncur; ++k) scale[k] = initialScalingVec[freeIdx[k]];
-            } else {
-                for (int i = 0; i < Ndim; ++i) if (!cI[i]) scale.push_back(initialScalingVec[i]);
-                scale.resize(ncur, 1.0);
-            }
-            D.setIdentity(&scale);
-        } else {
-            D.setIdentity();
-        }
-        tc.stop();
-        {
-            PhaseClock t(prof_slot(profile, kProfGrad));
-            objPtr->gradientApproximationRecur(X, dX, dFdX, cX, cI);
-            if (profile) profile[kProfGradCalls] += 1;
-        }
-        PhaseClock tc2(det_slot(kDetCopyBack));
-        bool cont = false;
-        for (int k : fk) {
-            if ((std::fabs(X[k] - Xlb[k]) < bndTol) && (dFdX[k] < 0)) cont = true;
-            else if ((std::fabs(X[k] - Xub[k]) < bndTol) && (dFdX[k] > 0)) cont = true;
-        }
-        if (freeIdxLive) {
-            Nconst = Ndim - ncur;
-        } else {
-            Nconst = 0;
-            for (int i = 0; i < Ndim; ++i) Nconst += cI[i];
-        }
-        if (Nconst == 0) recurFlag = false;
-        optimFlag = cont;
-        if (verbose > 0 && comm_rank() == ROOT_ID)
-            std::cout << (cont ? "     Optimization continuing after recursive boundary optimization."
-                               : "     Optimization exiting after recursive boundary optimization.")
-                      << std::endl;
-    } else if (nr == 0) {
-        // the coordinates frozen here stay frozen (as in the reference): cI no longer matches
-        // the levels above, so they fall back to the full walk
-        freeIdxLive = false;
-        optimFlag = false;
-        if (verbose > 0 && comm_rank() == ROOT_ID) std::cout << "      NO VARIABLES LEFT TO OPTIMIZE!!!! " << std::endl;
-    }
+    Policy pol{*this};
+    ActiveSetRecursion<Policy>(pol, pol.params(), objPtr, optimFlag, recurFlag, totalIter)
+        .assess(F, X, p, dFdX, D, Xlb, Xub, dX, cX, cI);
 }
 
 void BFGS_Bnd::mainBFGSLoop(double& F, vector<double>& X, vector<double>& dFdX, DenseInverseHessian& D,
                             vector<double>& Xlb, vector<double>& Xub, vector<double>& dX, vector<double>& cX,
                             vector<bool>& cI, bool& optimFlag, int& recurFlag) {
     // BFGS_bnd_linesearch.cpp:116-201
-    const int n = (int)X.size();
-    std::vector<double> p(n), pnext, Xprev(n);
-    bool have_next = false;
-    int iter = 0;
-    double xdiff = xMinDiff * 2, gnorm = 2 * minGrad2Norm;
-    while (optimFlag && iter < maxIter && xdiff > xMinDiff && gnorm > minGrad2Norm && totalIter < maxIter) {
-        if (verbose > 0 && comm_rank() == ROOT_ID)
-            std::cout << std::endl << "Iter = " << iter << " of bounded BFGS search starting with previous F = " << F
-                      << "." << std::endl;
-        // p = -D g (:142-143); after an iteration without recursion it came out of the update's
-        // pass (the same bits: D and g are what the update left)
-        if (have_next) {
-            p.swap(pnext);
-        } else {
-            PhaseClock t(prof_slot(profile, kProfUpdate));
-            D.direction(dFdX, p);
-        }
-        double alpha = 0, Fopt = 0;
-        {
-            PhaseClock t(prof_slot(profile, kProfLineSearch));
-            cubicInterpolationLineSearchBnd(X, Xlb, Xub, F, dFdX, p, cX, cI, alpha, Fopt);
-        }
-        PhaseClock tl(det_slot(kDetIterLoops));
-        for (int i = 0; i < n; ++i) { Xprev[i] = X[i]; X[i] = X[i] + alpha * p[i]; }
-        F = Fopt;
-        {
-            // per-iteration scratch (not live across the recursion below, so one set per thread)
-            thread_local std::vector<double> gprev, s, y;
-            gprev.assign(dFdX.begin(), dFdX.end());
-            s.resize(n);
-            y.resize(n);
-            tl.stop();
-            {
-                PhaseClock t(prof_slot(profile, kProfGrad));
-                objPtr->gradientApproximationRecur(X, dX, dFdX, cX, cI);
-                if (profile) profile[kProfGradCalls] += 1;
-            }
-            for (int i = 0; i < n; ++i) { s[i] = alpha * p[i]; y[i] = dFdX[i] - gprev[i]; }
-            PhaseClock t(prof_slot(profile, kProfUpdate));
-            D.update(y, s, &dFdX, &pnext);
-        }
-        assessRecursed = false;
-        pnextHeld = &pnext;
-        boundaryAssessment(F, X, p, dFdX, D, Xlb, Xub, dX, cX, cI, optimFlag, recurFlag);
-        pnextHeld = nullptr;
-        // a recursion reset D to I and recomputed the gradient: the fused direction is stale
-        have_next = !assessRecursed;
-        if (!have_next) std::vector<double>().swap(pnext);
-        // the step's sum |X - Xprev| and the gradient's sum of squares: two independent
-        // sequential chains (each in the reference's order), one loop
-        PhaseClock tl2(det_slot(kDetIterLoops));
-        xdiff = 0;
-        double gg = 0.0;
-        for (int i = 0; i < n; ++i) {
-            xdiff += std::fabs(X[i] - Xprev[i]);
-            gg = gg + dFdX[i] * dFdX[i];
-        }
-        gnorm = std::sqrt(gg);
-        if (fTrace) fTrace->push_back(F);
-        if (verbose > 1 && comm_rank() == ROOT_ID) {
-            std::cout << "  Step completed with F = " << F << " and mean abs xdiff is " << xdiff
-                      << " and the grad2norm = " << gnorm << std::endl << "  X = ";
-            print_vec(X);
-        }
-        iter = iter + 1;
-        totalIter = totalIter + 1;
-    }
+    Policy pol{*this};
+    ActiveSetRecursion<Policy>(pol, pol.params(), objPtr, optimFlag, recurFlag, totalIter)
+        .mainLoop(F, X, dFdX, D, Xlb, Xub, dX, cX, cI);
 }
 
 void BFGS_Bnd::findMinBnd(vector<double>& X, vector<double>& Xlb, vector<double>& Xub, double& f0, double& fOpt) {
     // the active-set recursion goes one level deeper per frozen coordinate (about 11k levels
     // at n = 16384, SURVEY 8(d) cfg 5): run it on a thread with a stack sized for that
     PhaseClock total(prof_slot(profile, kProfTotal));
-    depth = 0;
     run_deep([&] {
-        for (double& v : g_det) v = 0.0;
+        double* det = bnd_detail_all();
+        for (int k = 0; k < kDetCount; ++k) det[k] = 0.0;
         for (int k = 0; k < kRdCount; ++k)
             if (double* s = recur_detail(k)) *s = 0.0;
         findMinBndBody(X, Xlb, Xub, f0, fOpt);
-        if (det_slot(0)) {
+        if (bnd_detail_slot(0)) {
             std::fprintf(stderr, "[pnol_amd] BFGS_Bnd host detail (s): freeze %.3f gather+alloc %.3f copyback %.3f iter-loops %.3f\n",
-                         g_det[kDetFreeze], g_det[kDetGather], g_det[kDetCopyBack], g_det[kDetIterLoops]);
+                         det[kDetFreeze], det[kDetGather], det[kDetCopyBack], det[kDetIterLoops]);
             std::fprintf(stderr, "[pnol_amd] Recur FD gradient detail (s): build %.3f check %.3f device %.3f redo %.3f gather %.3f\n",
                          *recur_detail(kRdBuild), *recur_detail(kRdCheck), *recur_detail(kRdDevice),
                          *recur_detail(kRdRedo), *recur_detail(kRdGather));
@@ -449,54 +211,9 @@ void BFGS_Bnd::findMinBnd(vector<double>& X, vector<double>& Xlb, vector<double>
 void BFGS_Bnd::findMinBndBody(vector<double>& X, vector<double>& Xlb, vector<double>& Xub, double& f0,
                               double& fOpt) {
     // BFGS_bnd_linesearch.cpp:15-113
-    totalIter = 0;
-    if (verbose >= 0 && comm_rank() == ROOT_ID) {
-        std::cout << std::endl << "  Starting bounded BFGS with line search. " << std::endl << "  X0 = ";
-        print_vec(X);
-    }
-    const int n = (int)X.size();
-    checkBoxBounds(X, Xlb, Xub);
-    std::vector<double> cX(n, 0.0), X0 = X;
-    std::vector<bool> cI(n, false);
-    std::vector<double> dX(n, dXGrad);
-    if (!dXGradVec.empty())
-        for (int i = 0; i < n; ++i) dX[i] = dXGradVec[i];
-    std::vector<double> dFdX(n, 0.0);
-    pnol_ctx* ctx = require_ctx();
-    DenseInverseHessian D(ctx, n, updateMode);
-    if (initHessFD) {
-        init_from_fd_hessian(objPtr, X, dXHess, D);
-    } else if (!initialScalingVec.empty()) {
-        D.setIdentity(&initialScalingVec);
-    } else {
-        D.setIdentity();
-    }
-    {
-        PhaseClock t(prof_slot(profile, kProfGrad));
-        objPtr->gradientApproximationRecur(X, dX, dFdX, cX, cI);
-        if (profile) profile[kProfGradCalls] += 1;
-    }
-    double F = objPtr->objEvalRecur(X, cX, cI);
-    f0 = F;
     bool optimFlag = true;
     int recurFlag = 0;
-    freeIdx.resize(n);
-    for (int i = 0; i < n; ++i) freeIdx[i] = i;
-    freeIdxLive = true;
-    try {
-        mainBFGSLoop(F, X, dFdX, D, Xlb, Xub, dX, cX, cI, optimFlag, recurFlag);
-    } catch (...) {
-        freeIdxLive = false;
-        throw;
-    }
-    freeIdxLive = false;
-    std::vector<int>().swap(freeIdx);
-    fOpt = F;
-    if (verbose >= 0 && comm_rank() == ROOT_ID) {
-        std::cout << std::endl << "  Completed bounded BFGS." << std::endl << "  X0 = ";
-        print_vec(X0);
-        std::cout << "  Xopt = ";
-        print_vec(X);
-        std::cout << "  f0 = " << f0 << ", fOpt = " << fOpt << std::endl << std::endl;
-    }
+    Policy pol{*this};
+    ActiveSetRecursion<Policy>(pol, pol.params(), objPtr, optimFlag, recurFlag, totalIter)
+        .findMinBody(X, Xlb, Xub, f0, fOpt);
 }

@@ -8,34 +8,10 @@
 #include <iostream>
 #include <stdexcept>
 
-#include "../pnol_comm.hpp"
 #include "BFGS_with_bnd_linesearch_MPI.hpp"
-#include "dense_hessian.hpp"
-#include "line_points.hpp"
+#include "bfgs_common.hpp"
 
 using namespace pnol;
-
-namespace {
-
-void vector_min(const std::vector<double>& v, double& val, int& idx) {
-    val = v[0]; idx = 0;
-    for (size_t i = 1; i < v.size(); ++i) if (v[i] < val) { val = v[i]; idx = (int)i; }
-}
-double vector_max(const std::vector<double>& v) {
-    double m = v[0];
-    for (size_t i = 1; i < v.size(); ++i) if (v[i] > m) m = v[i];
-    return m;
-}
-void linspace(double a, double b, int N, std::vector<double>& v) {
-    v.resize(N);
-    for (int i = 0; i < N; ++i) v[i] = a + i * (b - a) / (N - 1);
-}
-void print_vec(const std::vector<double>& v) {
-    for (double x : v) std::printf("%.17g ", x);
-    std::printf("\n");
-}
-
-}  // namespace
 
 void checkAlphaPoolBnd(bool& bndIndicator, vector<double>& alphaPool, vector<double>& X, vector<double>& Xlb,
                        vector<double>& Xub, vector<double>& p, vector<double>&, vector<bool>&) {
@@ -56,24 +32,21 @@ void checkAlphaPoolBnd(bool& bndIndicator, vector<double>& alphaPool, vector<dou
 double BFGSBnd_MPI::lineSearchObj(double alpha, vector<double>& X, vector<double>& p, vector<double>& cX,
                                   vector<bool>& cI) {
     // :246-258
-    std::vector<double> Xa(X.size());
-    for (size_t i = 0; i < X.size(); ++i) Xa[i] = X[i] + alpha * p[i];
+    std::vector<double> Xa;
+    line_point(X, p, alpha, Xa);
     return objPtr->objEvalRecur(Xa, cX, cI);
 }
 
 void BFGSBnd_MPI::evalAlphaPoolMPI(vector<double>& alphaPool, vector<double>& phiPool, vector<double>& X,
                                    vector<double>& p, vector<double>& cX, vector<bool>& cI) {
     // :262-354: entry k is owned by rank k mod P; one allgather of ceil(N/P) values per rank
-    const int N = (int)phiPool.size();
-    const int P = comm_size(), r = comm_rank();
-    const int per = (N + P - 1) / P;
-    std::vector<double> mine(per, 0.0), all((size_t)per * P, 0.0);
+    const PoolSlots ps((int)phiPool.size(), comm_size());
+    std::vector<double> mine(ps.per, 0.0);
     std::vector<double> mya;   // this rank's entries, one batch
-    for (int k = r; k < N; k += P) mya.push_back(alphaPool[k]);
+    for (int k = comm_rank(); k < ps.N; k += ps.P) mya.push_back(alphaPool[k]);
     eval_line_points_recur(objPtr, X, p, mya.data(), (int)mya.size(), cX, cI, mine.data());
-    check(comm_allgather_host(nullptr, mine.data(), all.data(), (size_t)per), "allgather(alpha pool)");
-    for (int k = 0; k < N; ++k) phiPool[k] = all[(size_t)(k % P) * per + k / P];
-    for (int k = 0; k < N; ++k)
+    pool_exchange(ps, 1, mine, phiPool.data());
+    for (int k = 0; k < ps.N; ++k)
         if (phiPool[k] != phiPool[k] || std::isinf(phiPool[k]))
             throw std::runtime_error("BFGSBnd_MPI: line search produced a NaN/inf objective value");
 }
@@ -81,93 +54,16 @@ void BFGSBnd_MPI::evalAlphaPoolMPI(vector<double>& alphaPool, vector<double>& ph
 void BFGSBnd_MPI::secantLineSearchBnd(vector<double>& X, vector<double>& Xlb, vector<double>& Xub, double FX,
                                       vector<double>& dFdX, vector<double>& p, double& alphaOpt, double& Fopt,
                                       vector<double>& cX, vector<bool>& cI) {
-    // :358-660
-    const int Npool = poolSize > 0 ? poolSize : comm_size();
-    std::vector<double> alphaPool(Npool, 0.0), phiPool(Npool, 0.0), alphaPoolPrev(Npool, -1.0),
-        phiPoolPrev(Npool, 0.0), slope(Npool, 0.0);
-    alphaOpt = 0;
-    Fopt = FX;
-    const double alpha0 = 0, phi0 = FX, dphi0 = seq_dot(dFdX, p);
-    bool bndIndicator = false;
-
-    int idxMin = -(int)std::ceil((Npool - 1.0) / 2.0);
-    const int idxMax = (int)std::floor((Npool - 1.0) / 2.0);
-    double r = std::pow(maxAlphaMult, 1.0 / (double)idxMax);
-    for (int k = 0, idx = idxMin; k < Npool; ++k, ++idx) alphaPool[k] = alphaGuess * std::pow(r, idx);
-
-    bool firstFlag = true, zoomFlag = false;
-    for (int iter = 0; iter < maxIterLineSearch && firstFlag; ++iter) {
-        checkAlphaPoolBnd(bndIndicator, alphaPool, X, Xlb, Xub, p, cX, cI);
-        evalAlphaPoolMPI(alphaPool, phiPool, X, p, cX, cI);
-        // 1. sufficient decrease
-        for (int i = 0; i < Npool; ++i)
-            if (phiPool[i] > phi0 + c1 * alphaPool[i] * dphi0) { zoomFlag = true; firstFlag = false; }
-        // 2. curvature against the secant slopes
-        slope[0] = (phiPool[0] - phi0) / (alphaPool[0] - alpha0);
-        for (int i = 1; i < Npool; ++i) slope[i] = (phiPool[i] - phiPool[i - 1]) / (alphaPool[i] - alphaPool[i - 1]);
-        if (firstFlag)
-            for (int i = 0; i < Npool; ++i)
-                if (std::fabs(slope[i]) <= std::fabs(c2 * dphi0)) { zoomFlag = false; firstFlag = false; }
-        // 3. a non-negative secant slope brackets a minimum
-        if (firstFlag)
-            for (int i = 0; i < Npool; ++i)
-                if (slope[i] >= 0) { zoomFlag = true; firstFlag = false; }
-        // 4. extend the pool, unless it was clipped to the box
-        if (firstFlag && !bndIndicator) {
-            const double alphaMax = vector_max(alphaPool);
-            r = std::pow(maxAlphaMult, 1.0 / (double)Npool);
-            for (int i = 0; i < Npool; ++i) {
-                alphaPoolPrev[i] = alphaPool[i];
-                phiPoolPrev[i] = phiPool[i];
-                const double power = i + 1;
-                alphaPool[i] = alphaMax * std::pow(r, power);
-            }
-        } else if (bndIndicator) {
-            firstFlag = false;
-            if (verbose && comm_rank() == ROOT_ID) {
-                std::cout << std::endl << "Line search reached boundary. Attempting to find an acceptable point in "
-                          << "the domain interior." << std::endl << "alpha = ";
-                print_vec(alphaPool);
-                std::cout << "phi = ";
-                print_vec(phiPool);
-            }
-        }
-    }
-
-    double alo, ahi, plo, phi;
-    if (alphaPoolPrev[0] < 0) {
-        findPoolBounds(alphaPool, phiPool, alpha0, phi0, alo, ahi, plo, phi);
-    } else {
-        std::vector<double> ae(2 * Npool), pe(2 * Npool);
-        for (int i = 0; i < Npool; ++i) {
-            ae[i] = alphaPoolPrev[i]; ae[i + Npool] = alphaPool[i];
-            pe[i] = phiPoolPrev[i]; pe[i + Npool] = phiPool[i];
-        }
-        findPoolBounds(ae, pe, alpha0, phi0, alo, ahi, plo, phi);
-    }
-
-    // zoom: Npool interior points of [alpha_lo, alpha_hi] per round (:547-648)
-    std::vector<double> alphaPool2(Npool + 2, 0.0), phiPool2(Npool + 2, 0.0);
-    for (int iter = 0; iter < maxIterLineSearch && zoomFlag; ++iter) {
-        linspace(alo, ahi, Npool + 2, alphaPool2);
-        phiPool2[0] = plo; phiPool2[Npool + 1] = phi;
-        alphaPool2[0] = alo; alphaPool2[Npool + 1] = ahi;
-        for (int i = 0; i < Npool; ++i) { alphaPool[i] = alphaPool2[i + 1]; phiPool[i] = phiPool2[i + 1]; }
-        evalAlphaPoolMPI(alphaPool, phiPool, X, p, cX, cI);
-        for (int i = 0; i < Npool; ++i) { alphaPool2[i + 1] = alphaPool[i]; phiPool2[i + 1] = phiPool[i]; }
-        for (int i = 0; i < Npool; ++i)
-            slope[i] = (phiPool2[i + 1] - phiPool2[i]) / (alphaPool2[i + 1] - alphaPool2[i]);
-        for (int i = 0; i < Npool; ++i)
-            if (std::fabs(slope[i]) <= std::fabs(c2 * dphi0)) zoomFlag = false;
-        if (zoomFlag) findPoolBounds(alphaPool2, phiPool2, alpha0, phi0, alo, ahi, plo, phi);
-        if (vector_max(alphaPool2) < alphaMin) zoomFlag = false;
-    }
-
-    // the minimum of the last evaluated pool (:651-655)
-    double phiMin;
-    vector_min(phiPool, phiMin, idxMin);
-    alphaOpt = alphaPool[idxMin];
-    Fopt = phiMin;
+    // :358-660: pools clipped to the box, zoom stopped below alphaMin, and the result is the
+    // minimum of the last evaluated pool (:651-655)
+    SecantSearch o;
+    o.c1 = c1; o.c2 = c2; o.maxAlphaMult = maxAlphaMult; o.alphaGuess = alphaGuess;
+    o.maxIterLineSearch = maxIterLineSearch; o.Npool = poolSize > 0 ? poolSize : comm_size();
+    o.Xlb = &Xlb; o.Xub = &Xub; o.verbose = verbose;
+    o.alphaMinStop = true; o.alphaMin = alphaMin;
+    o.resultFromZoomPool = false; o.fixZeroPool = false;
+    secant_pool_search(o, [&](vector<double>& ap, vector<double>& pp) { evalAlphaPoolMPI(ap, pp, X, p, cX, cI); }, X,
+                       FX, dFdX, p, alphaOpt, Fopt);
 }
 
 void BFGSBnd_MPI::boundaryAssessment(double& F, vector<double>& X, vector<double>& p, vector<double>& dFdX,

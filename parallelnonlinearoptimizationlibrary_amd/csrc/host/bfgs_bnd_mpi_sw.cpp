@@ -7,28 +7,13 @@
 #include <cstdio>
 #include <iostream>
 
-#include "../pnol_comm.hpp"
 #include "BFGS_bnd_linesearch_MPI_SW.hpp"
+#include "bfgs_common.hpp"
 #include "deep_stack.hpp"
-#include "dense_hessian.hpp"
-#include "line_points.hpp"
 
 using namespace pnol;
 
 namespace {
-
-void vector_min(const std::vector<double>& v, double& val, int& idx) {
-    val = v[0]; idx = 0;
-    for (size_t i = 1; i < v.size(); ++i) if (v[i] < val) { val = v[i]; idx = (int)i; }
-}
-void linspace(double a, double b, int N, std::vector<double>& v) {
-    v.resize(N);
-    for (int i = 0; i < N; ++i) v[i] = a + i * (b - a) / (N - 1);
-}
-void print_vec(const std::vector<double>& v) {
-    for (double x : v) std::printf("%.17g ", x);
-    std::printf("\n");
-}
 
 // computeZoomPool, BFGS_bnd_linesearch_MPI_SW.cpp:434-482: Npool points from alpha_a to
 // alpha_b, one of them the cubic-interpolation minimiser; the two ends are already known
@@ -77,15 +62,15 @@ BFGS_Bnd_MPI_SW::BFGS_Bnd_MPI_SW()
 
 double BFGS_Bnd_MPI_SW::lineSearchObj(double alpha, vector<double>& X, vector<double>& p, vector<double>& cX,
                                       vector<bool>& cI) {
-    std::vector<double> Xa(X.size());
-    for (size_t i = 0; i < X.size(); ++i) Xa[i] = X[i] + alpha * p[i];
+    std::vector<double> Xa;
+    line_point(X, p, alpha, Xa);
     return objPtr->objEvalRecur(Xa, cX, cI);
 }
 
 double BFGS_Bnd_MPI_SW::lineSearchFDDerivative(double alpha, double phialpha, vector<double>& X, vector<double>& p,
                                                vector<double>& cX, vector<bool>& cI) {
-    std::vector<double> Xa(X.size());
-    for (size_t i = 0; i < X.size(); ++i) Xa[i] = X[i] + (alpha + dalpha) * p[i];
+    std::vector<double> Xa;
+    line_point(X, p, alpha + dalpha, Xa);
     const double Fa = objPtr->objEvalRecur(Xa, cX, cI);
     return (Fa - phialpha) / dalpha;
 }
@@ -94,10 +79,10 @@ void BFGS_Bnd_MPI_SW::evaluateAlphaPoolAndDerivatives(vector<double>& ap, vector
                                                       vector<double>& cX, vector<bool>& cI, vector<double>& pp,
                                                       vector<double>& dp) {
     // :599-699: entry k is owned by rank k mod P; (phi, dphi) pairs, one allgather
-    const int N = (int)ap.size();
-    const int P = comm_size(), r = comm_rank();
-    const int per = (N + P - 1) / P > 0 ? (N + P - 1) / P : 1;
-    std::vector<double> mine(2 * (size_t)per, 0.0), all(2 * (size_t)per * P, 0.0);
+    const int N = (int)ap.size(), r = comm_rank();
+    const PoolSlots ps(N, comm_size());
+    const int P = ps.P, per = ps.per;
+    std::vector<double> mine(2 * (size_t)per, 0.0);
     // this rank's entries as one batch of (alpha, alpha + dalpha) pairs, in the reference's order
     std::vector<double> mya, fv;
     for (int k = r; k < N; k += P) { mya.push_back(ap[k]); mya.push_back(ap[k] + dalpha); }
@@ -115,11 +100,11 @@ void BFGS_Bnd_MPI_SW::evaluateAlphaPoolAndDerivatives(vector<double>& ap, vector
         mine[2 * q] = phi;
         mine[2 * q + 1] = dphi;
     }
-    check(comm_allgather_host(nullptr, mine.data(), all.data(), 2 * (size_t)per), "allgather(alpha pool)");
+    std::vector<double> pool(2 * (size_t)N);
+    pool_exchange(ps, 2, mine, pool.data());
     for (int k = 0; k < N; ++k) {
-        const size_t at = 2 * ((size_t)(k % P) * per + k / P);
-        pp[k] = all[at];
-        dp[k] = all[at + 1];
+        pp[k] = pool[2 * (size_t)k];
+        dp[k] = pool[2 * (size_t)k + 1];
     }
     for (int k = 0; k < N; ++k)
         if (pp[k] == 1e10) {
@@ -256,123 +241,49 @@ void BFGS_Bnd_MPI_SW::cubicInterpolationLineSearchBnd(vector<double>& X, vector<
     }
 }
 
-void BFGS_Bnd_MPI_SW::boundaryAssessment(double& F, vector<double>& X, vector<double>& p, vector<double>& dFdX,
-                                         DenseInverseHessian& D, vector<double>& Xlb, vector<double>& Xub,
-                                         vector<double>& dX, vector<double>& cX, vector<bool>& cI) {
-    // :741-967 (BFGS_Bnd's recursion with the gradients sharded)
-    const int ncur = (int)X.size();
-    const int Ndim = (int)cX.size();
-    std::vector<bool> cIcur(ncur, false);
-    std::vector<int> frozen;
-    bool bndFlag = false;
-    int icur = 0;
-    for (int i = 0; i < Ndim; ++i) {
-        if (cI[i]) continue;
-        if ((std::fabs(X[icur] - Xlb[icur]) < bndTol) && ((p[icur] < 0) || (dFdX[icur] > 0))) {
-            bndFlag = true; cI[i] = true; cX[i] = X[icur]; cIcur[icur] = true; frozen.push_back(i);
-        } else if ((std::fabs(X[icur] - Xub[icur]) < bndTol) && ((p[icur] > 0) || (dFdX[icur] < 0))) {
-            bndFlag = true; cI[i] = true; cX[i] = X[icur]; cIcur[icur] = true; frozen.push_back(i);
-        }
-        icur++;
+// BFGS_Bnd_MPI_SW's side of the shared active-set recursion (bfgs_common.hpp): the sharded
+// Recur gradient, the pooled Wolfe search above, D row-sharded, D.update then D.direction
+struct BFGS_Bnd_MPI_SW::Policy {
+    static constexpr bool kShardD = true, kFusedDirection = false, kDetailClocks = false;
+    static constexpr int kStepTextAbove = 0, kRecursedTextAbove = 1;
+    BFGS_Bnd_MPI_SW& b;
+    void gradient(vector<double>& X, vector<double>& dX, vector<double>& dFdX, vector<double>& cX, vector<bool>& cI) {
+        b.objPtr->gradientApproximationMPIRecur(X, dX, dFdX, cX, cI);
     }
-    int Nconst = 0;
-    for (int i = 0; i < Ndim; ++i) Nconst += cI[i];
-    if (bndFlag && verbose > 0 && procID == ROOT_ID) {
+    void lineSearch(vector<double>& X, vector<double>& Xlb, vector<double>& Xub, double F, vector<double>& dFdX,
+                    vector<double>& p, vector<double>& cX, vector<bool>& cI, double& alpha, double& Fopt) {
+        b.cubicInterpolationLineSearchBnd(X, Xlb, Xub, F, dFdX, p, cX, cI, alpha, Fopt);
+    }
+    const char* startText() const { return "  Starting parallel bounded BFGS with line search. "; }
+    bool announcesBoundary(int verbose) const { return verbose > 0; }
+    void boundaryText(size_t nfrozen, const vector<double>& X, double F) const {
         std::cout << std::endl << "Optimizer reached box boundary and found that the steepest descent is directed "
-                  << "outside of the boundary at " << frozen.size() << " coordinate(s)." << std::endl << "    X = ";
+                  << "outside of the boundary at " << nfrozen << " coordinate(s)." << std::endl << "    X = ";
         print_vec(X);
         std::cout << "    F = " << F << std::endl;
     }
-    const int nr = Ndim - Nconst;
-    if (bndFlag && nr > 0) {
-        double FR = F;
-        std::vector<double> XR, gR, lbR, ubR, dXR;
-        for (icur = 0; icur < ncur; ++icur)
-            if (!cIcur[icur]) {
-                XR.push_back(X[icur]); gR.push_back(dFdX[icur]); lbR.push_back(Xlb[icur]);
-                ubR.push_back(Xub[icur]); dXR.push_back(dX[icur]);
-            }
-        // the reduced problem starts along steepest descent (scaled if a scaling was set)
-        DenseInverseHessian DR(D, nr, updateMode, true);   // D's buffer: it is reset on return
-        if (!initialScalingVec.empty()) {
-            std::vector<double> scaleR;
-            for (int i = 0; i < Ndim; ++i) if (!cI[i]) scaleR.push_back(initialScalingVec[i]);
-            DR.setIdentity(&scaleR);
-        } else {
-            DR.setIdentity();
-        }
-        recurFlag = true;
-        mainBFGSLoop(FR, XR, gR, DR, lbR, ubR, dXR, cX, cI);
-        int ir = 0;
-        for (icur = 0; icur < ncur; ++icur)
-            if (!cIcur[icur]) {
-                F = FR; X[icur] = XR[ir]; dFdX[icur] = gR[ir]; Xlb[icur] = lbR[ir]; Xub[icur] = ubR[ir];
-                dX[icur] = dXR[ir];
-                ir++;
-            }
-        for (int k : frozen) cI[k] = false;
-        if (!initialScalingVec.empty()) {
-            std::vector<double> scale;
-            for (int i = 0; i < Ndim; ++i) if (!cI[i]) scale.push_back(initialScalingVec[i]);
-            scale.resize(ncur, 1.0);
-            D.setIdentity(&scale);
-        } else {
-            D.setIdentity();
-        }
-        objPtr->gradientApproximationMPIRecur(X, dX, dFdX, cX, cI);
-        bool cont = false;
-        for (icur = 0; icur < ncur; ++icur)
-            if (cIcur[icur]) {
-                if ((std::fabs(X[icur] - Xlb[icur]) < bndTol) && (dFdX[icur] < 0)) cont = true;
-                else if ((std::fabs(X[icur] - Xub[icur]) < bndTol) && (dFdX[icur] > 0)) cont = true;
-            }
-        Nconst = 0;
-        for (int i = 0; i < Ndim; ++i) Nconst += cI[i];
-        if (Nconst == 0) recurFlag = false;
-        optimFlag = cont;
-        if (verbose > 1 && procID == ROOT_ID)
-            std::cout << (cont ? "     Optimization continuing after recursive boundary optimization."
-                               : "     Optimization exiting after recursive boundary optimization.")
-                      << std::endl;
-    } else if (nr == 0) {
-        optimFlag = false;
-        if (verbose > 1 && procID == ROOT_ID) std::cout << "      NO VARIABLES LEFT TO OPTIMIZE!!!! " << std::endl;
+    BndParams params() const {
+        return BndParams{b.bndTol, b.dXGrad, b.dXHess, b.xMinDiff, b.minGrad2Norm, b.maxIter, b.updateMode, b.verbose,
+                         b.initHessFD, &b.dXGradVec, &b.initialScalingVec, nullptr, nullptr};
     }
+};
+
+void BFGS_Bnd_MPI_SW::boundaryAssessment(double& F, vector<double>& X, vector<double>& p, vector<double>& dFdX,
+                                         DenseInverseHessian& D, vector<double>& Xlb, vector<double>& Xub,
+                                         vector<double>& dX, vector<double>& cX, vector<bool>& cI) {
+    // :741-967
+    Policy pol{*this};
+    ActiveSetRecursion<Policy>(pol, pol.params(), objPtr, optimFlag, recurFlag, totalIter)
+        .assess(F, X, p, dFdX, D, Xlb, Xub, dX, cX, cI);
 }
 
 void BFGS_Bnd_MPI_SW::mainBFGSLoop(double& F, vector<double>& X, vector<double>& dFdX, DenseInverseHessian& D,
                                    vector<double>& Xlb, vector<double>& Xub, vector<double>& dX, vector<double>& cX,
                                    vector<bool>& cI) {
     // :116-207
-    const int n = (int)X.size();
-    std::vector<double> gprev = dFdX, p(n), s(n), y(n), Xprev(n);
-    int iter = 0;
-    double xdiff = xMinDiff * 2, gnorm = 2 * minGrad2Norm;
-    while (optimFlag && iter < maxIter && xdiff > xMinDiff && gnorm > minGrad2Norm && totalIter < maxIter) {
-        if (verbose > 0 && procID == ROOT_ID)
-            std::cout << std::endl << "Iter = " << iter << " of bounded BFGS search starting with previous F = " << F
-                      << "." << std::endl;
-        D.direction(dFdX, p);
-        double alpha = 0, Fopt = 0;
-        cubicInterpolationLineSearchBnd(X, Xlb, Xub, F, dFdX, p, cX, cI, alpha, Fopt);
-        for (int i = 0; i < n; ++i) { Xprev[i] = X[i]; X[i] = X[i] + alpha * p[i]; }
-        F = Fopt;
-        gprev = dFdX;
-        objPtr->gradientApproximationMPIRecur(X, dX, dFdX, cX, cI);
-        for (int i = 0; i < n; ++i) { s[i] = alpha * p[i]; y[i] = dFdX[i] - gprev[i]; }
-        D.update(y, s, nullptr, nullptr);
-        boundaryAssessment(F, X, p, dFdX, D, Xlb, Xub, dX, cX, cI);
-        xdiff = 0;
-        for (int i = 0; i < n; ++i) xdiff += std::fabs(X[i] - Xprev[i]);
-        gnorm = std::sqrt(seq_dot(dFdX, dFdX));
-        if (verbose > 0 && procID == ROOT_ID) {
-            std::cout << "  Step completed with F = " << F << " and mean abs xdiff is " << xdiff
-                      << " and the grad2norm = " << gnorm << std::endl;
-            if (verbose > 1) { std::cout << "  X = "; print_vec(X); }
-        }
-        iter = iter + 1;
-        totalIter = totalIter + 1;
-    }
+    Policy pol{*this};
+    ActiveSetRecursion<Policy>(pol, pol.params(), objPtr, optimFlag, recurFlag, totalIter)
+        .mainLoop(F, X, dFdX, D, Xlb, Xub, dX, cX, cI);
 }
 
 void BFGS_Bnd_MPI_SW::findMinBnd(vector<double>& X, vector<double>& Xlb, vector<double>& Xub, double& f0,
@@ -386,35 +297,9 @@ void BFGS_Bnd_MPI_SW::findMinBnd(vector<double>& X, vector<double>& Xlb, vector<
 void BFGS_Bnd_MPI_SW::findMinBndBody(vector<double>& X, vector<double>& Xlb, vector<double>& Xub, double& f0,
                                      double& fOpt) {
     // :12-113
-    totalIter = 0;
     Nprocs = comm_size();
     procID = comm_rank();
-    if (verbose >= 0 && procID == ROOT_ID) {
-        std::cout << std::endl << "  Starting parallel bounded BFGS with line search. " << std::endl << "  X0 = ";
-        print_vec(X);
-    }
-    const int n = (int)X.size();
-    checkBoxBounds(X, Xlb, Xub);
-    std::vector<double> cX(n, 0.0), X0 = X, dX(n, dXGrad), dFdX(n, 0.0);
-    std::vector<bool> cI(n, false);
-    if (!dXGradVec.empty())
-        for (int i = 0; i < n; ++i) dX[i] = dXGradVec[i];
-    DenseInverseHessian D(require_ctx(), n, updateMode, true);   // row-sharded over the ranks
-    if (initHessFD) init_from_fd_hessian(objPtr, X, dXHess, D);
-    else if (!initialScalingVec.empty()) D.setIdentity(&initialScalingVec);
-    else D.setIdentity();
-    objPtr->gradientApproximationMPIRecur(X, dX, dFdX, cX, cI);
-    double F = objPtr->objEvalRecur(X, cX, cI);
-    f0 = F;
-    optimFlag = true;
-    recurFlag = 0;
-    mainBFGSLoop(F, X, dFdX, D, Xlb, Xub, dX, cX, cI);
-    fOpt = F;
-    if (verbose >= 0 && procID == ROOT_ID) {
-        std::cout << std::endl << "  Completed bounded BFGS." << std::endl << "  X0 = ";
-        print_vec(X0);
-        std::cout << "  Xopt = ";
-        print_vec(X);
-        std::cout << "  f0 = " << f0 << ", fOpt = " << fOpt << std::endl << std::endl;
-    }
+    Policy pol{*this};
+    ActiveSetRecursion<Policy>(pol, pol.params(), objPtr, optimFlag, recurFlag, totalIter)
+        .findMinBody(X, Xlb, Xub, f0, fOpt);
 }

@@ -16,6 +16,7 @@
 #include "../pnol_internal.hpp"
 #include "LevenbergMarquardt.hpp"
 #include "LevenbergMarquardtMPI.hpp"
+#include "bfgs_helpers.hpp"   // print_vec
 #include "device_util.hpp"
 
 using namespace pnol;
@@ -29,11 +30,6 @@ struct LMParams {
 };
 
 double norm2(const std::vector<double>& v) { return std::sqrt(seq_dot(v, v)); }
-
-void print_vec(const std::vector<double>& v) {
-    for (double x : v) std::printf("%.17g ", x);
-    std::printf("\n");
-}
 
 // Device state of one LM solve.  JT holds J column-major (one FD column per row, ld = ldjt,
 // n rows in natural column order).  LevMarqMPI: each rank evaluates its cost-balanced FD

@@ -322,6 +322,83 @@ def test_bfgs_bnd_mpi_sw_box_cases(ctx, oracle, case):
     assert res.fopt == reso.fopt
 
 
+@pytest.mark.parametrize("case", [
+    # test_bfgs_bnd_matches_oracle's multi-freeze geometries: several coordinates freeze at
+    # interior positions at once, so the in-place compaction of the reduced vectors is exercised
+    ("alternating", 12, [0.2, -0.2] * 6, [-0.3] * 12, [0.6] * 12),
+    ("upper-ramp", 16, list(np.linspace(-0.9, 0.9, 16)), [-1.0] * 16, [0.35] * 16),
+    ("interior-lower", 9, [1.5] * 9, [0.2, 1.2, 0.2, 1.3, 0.2, 1.1, 0.2, 1.4, 0.2], [2.0] * 9),
+])
+def test_bfgs_bnd_mpi_sw_multi_freeze_matches_oracle(ctx, oracle, case):
+    from parallelnonlinearoptimizationlibrary_amd import _lib as L
+    from parallelnonlinearoptimizationlibrary_amd.device import run_bfgs
+    name, n, x0, lb, ub = case
+    X, res = run_bfgs(_obj(ctx, L.OBJ_ROSENBROCK, n), x0, SW_P + [4], which=4, lb=lb, ub=ub)
+    Xo, reso = oracle.bfgs_bnd_mpi_sw_findmin(oracle.rosenbrock(n), x0, lb, ub, SW_P, 4)
+    print(f"{name}: fopt {res.fopt!r} vs {reso.fopt!r}, evals {res.evals} vs {reso.evals}")
+    assert np.array_equal(X, Xo), name
+    assert res.fopt == reso.fopt and res.evals == reso.evals
+
+
+# ---- the drop-in classes driven from C++ (tests/cpp/bfgs_family_cxx.cpp) -------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FAMILY = ["BFGS", "BFGS_MPI", "BFGSBnd_MPI", "BFGS_Bnd", "BFGS_Bnd_MPI_SW"]
+
+
+@pytest.fixture(scope="module")
+def family_exe(tmp_path_factory):
+    import subprocess
+    pkg = os.path.join(ROOT, "parallelnonlinearoptimizationlibrary_amd")
+    exe = str(tmp_path_factory.mktemp("bfgs_family") / "bfgs_family_cxx")
+    subprocess.run(["g++", "-O2", "-std=c++0x", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "cpp", "bfgs_family_cxx.cpp"), "-L", pkg, "-lpnol_amd", "-pthread",
+                    f"-Wl,-rpath,{pkg}", "-o", exe], check=True)
+    return exe
+
+
+def test_bfgs_family_scaling_and_grad_vectors(family_exe):
+    """setinitialScalingVec / setGradVec of BFGS_Bnd and BFGS_Bnd_MPI_SW (the C drivers do not reach
+    them; the oracle has no scaling vector).  A scaling of all 1.0 with a dXGradVec of all dXGrad
+    is bitwise the run with neither set; the alternating pair is bitwise the run recorded from
+    this program (--record) on the commit before the family shared its code
+    (tests/golden/bfgs_family_parent.json)."""
+    import subprocess
+    r = subprocess.run([family_exe, "scaling"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    rows = {}
+    for ln in r.stdout.splitlines():
+        if ln.startswith("R "):
+            _, cls, variant, evals, f0, fopt, *x = ln.split()
+            rows[cls, variant] = {"evals": int(evals), "f0": f0, "fOpt": fopt, "X": x}
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "bfgs_family_parent.json")))
+    for cls, n in (("BFGS_Bnd", 12), ("BFGS_Bnd_MPI_SW", 10)):
+        assert len(rows[cls, "none"]["X"]) == n
+        assert rows[cls, "unit"] == rows[cls, "none"], cls
+        assert rows[cls, "pair"] == gold[cls], cls
+        assert rows[cls, "pair"] != rows[cls, "none"], cls   # the pair does change the run
+
+
+# each class at its loudest verbosity, and the two bounded classes at the levels where their
+# thresholds differ (the step line: BFGS_Bnd above 1, the pooled class above 0; the lines after a
+# recursion: above 0 / above 1; the boundary announcement: any non-zero level / above 0)
+FAMILY_TEXT = [(cls, None) for cls in FAMILY] + [("BFGS_Bnd", 1), ("BFGS_Bnd", -1), ("BFGS_Bnd_MPI_SW", 1),
+                                                 ("BFGS_Bnd_MPI_SW", 2)]
+
+
+@pytest.mark.parametrize("cls,level", FAMILY_TEXT)
+def test_bfgs_family_printed_text(family_exe, cls, level):
+    """Each class on Rosenbrock n = 3 ("lower-active", maxIter 6): stdout byte for byte the text
+    recorded on the commit before the family shared its code."""
+    import subprocess
+    r = subprocess.run([family_exe, "text", cls] + ([] if level is None else [str(level)]), capture_output=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr.decode()
+    name = f"bfgs_family_stdout_{cls}" + ("" if level is None else f"_v{level}") + ".txt"
+    gold = open(os.path.join(ROOT, "tests", "golden", name), "rb").read()
+    assert len(gold) > (200 if level is None else 50)
+    assert r.stdout == gold
+
+
 def test_gather_submatrix(ctx):
     """pnol_gather_submatrix_d: D[idx][idx] bitwise (BFGS_with_bnd_linsearch_MPI.cpp:832-840)."""
     import torch
