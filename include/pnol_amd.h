@@ -55,7 +55,7 @@ int pnol_default_ctx(pnol_ctx** out);
 /* Per-kernel HIP-event timers on the context's stream (off by default).  Names: "fd_jacobian",
  * "fd_ckpt", "fd_gradient", "linres_eval", "syrk", "syrk_reduce", "jtr", "solve", "hg",
  * "bfgs_pass", "allgather", "exchange_J", "exchange_A", "lm_batch", "simplex_batch",
- * "bfgs_batch".  total_ms sums the recorded launches since the last reset.  on = 2 times only
+ * "bfgs_batch", "bfgs_bnd_batch".  total_ms sums the recorded launches since the last reset.  on = 2 times only
  * "fd_jacobian", "fd_ckpt", "syrk", "exchange_J", "allgather", "hg" and "bfgs_pass" (fewer event
  * records between launches). */
 int pnol_ctx_enable_timers(pnol_ctx* ctx, int on);
@@ -433,6 +433,52 @@ int pnol_bfgs_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* params,
 int pnol_run_bfgs_batch(int kind, int n, double power, const double* p0, size_t len0, const double* p1, size_t len1,
                         long long nstart, const double* params, double* X, double* f0, double* fopt, double* gnorm,
                         int* iters, long long* evals);
+
+/* ---- batched box-bounded BFGS: many independent BFGS_Bnd solves in one launch ----------- */
+/* The largest n of a batched bounded solve: a lane's D, vectors and recursion stack,
+ * n^2 + n (n + 1) / 2 + 8 n doubles, live in LDS (64 lanes x 318 doubles = 159 KB at n = 12). */
+#define PNOL_BFGS_BND_BATCH_NMAX 12
+/* bit 8 of info: the start ended at a corner end (below) */
+#define PNOL_BFGS_BND_BATCH_CORNER 256
+/* nstart independent BFGS_Bnd::findMinBnd runs (BFGS_bnd_linesearch.cpp:15-750) of one scalar
+ * device objective -- PNOL_OBJ_ROSENBROCK, PNOL_OBJ_POWER or PNOL_OBJ_QUADRATIC; other kinds
+ * PNOL_ERR_UNSUPPORTED -- in one box shared by all starts, queued on the context stream with no
+ * host wait (timer "bfgs_bnd_batch"): one GPU lane runs one start's whole solve (checkBoxBounds,
+ * the FD gradient over the free coordinates, the bounded cubic-interpolation line search with its
+ * zoom, the exact update, the active-set recursion of boundaryAssessment as an explicit stack) in
+ * the reference's operation order.  params: HOST, 15 doubles in BFGS_Bnd::setParams order (c1,
+ * c2, dalpha, alphaGuess, alphaTol, alphaMult, maxIterLineSearch, bndTol, dXGrad, dXHess, maxIter,
+ * xMinDiff, minGrad2Norm, initHessFD, verbose); alphaMult, dXHess and verbose are accepted and
+ * ignored (nothing is printed), initHessFD != 0 is PNOL_ERR_UNSUPPORTED (D starts as the
+ * identity; per-coordinate FD steps, an initial scaling and the rank-2 update mode are not
+ * offered either), PNOL_ERR_ARG when maxIter or maxIterLineSearch is negative, NaN or does not
+ * fit an int.  Xlb / Xub: n device doubles each.  X: nstart * n device doubles, the starts in and
+ * the optima out; f0 / fopt: nstart doubles; iters: nstart ints, totalIter (the trips of all
+ * recursion levels); evals: nstart long longs, objEval calls the reference would have made from
+ * the first gradient on; info: nstart ints, bits 0-7 the deepest recursion level, bit 8
+ * (PNOL_BFGS_BND_BATCH_CORNER) a corner end.  Start s is BFGS_Bnd::findMinBnd from X[s] -- the
+ * same bits of X, f0, fOpt, iterations and evaluations, whatever batch it is in (Power with
+ * power != 2 calls the device pow and is not bitwise against the host) -- with one exception, the
+ * corner end: when an assessment at recursion depth >= 1 leaves no free coordinate, the reference
+ * keeps those coordinates marked constant while the levels above release only their own, and
+ * from then on reads past its reduced vectors (undefined behaviour).  The batch ends such a start
+ * at that assessment: X is the full-space point (every coordinate at a bound with an outward
+ * direction or gradient), fopt the level's F, iters and evals as counted up to there, bit 8 of
+ * info set; everything before is the reference's arithmetic.  No free coordinate left at depth 0
+ * is not a corner end and follows the reference.  1 <= n <= PNOL_BFGS_BND_BATCH_NMAX, a larger n
+ * PNOL_ERR_UNSUPPORTED; nstart <= 0 PNOL_ERR_ARG.  The reference has no batched form: this
+ * replaces a host loop of multi-start findMinBnd calls. */
+int pnol_bfgs_bnd_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* params, const double* Xlb,
+                                const double* Xub, long long nstart, double* X, double* f0, double* fopt, int* iters,
+                                long long* evals, int* info);
+/* The same with HOST pointers on the process default context: create the objective (kind, n,
+ * power, p0 / p1 as pnol_dobj_create), upload, solve, download, destroy.  Arguments are checked
+ * before any device use -- a box entry with Xlb > Xub (or a NaN) is PNOL_ERR_ARG;
+ * PNOL_ERR_NODEVICE without a gfx950 device. */
+int pnol_run_bfgs_bnd_batch(int kind, int n, double power, const double* p0, size_t len0, const double* p1,
+                            size_t len1, long long nstart, const double* params, const double* Xlb,
+                            const double* Xub, double* X, double* f0, double* fopt, int* iters, long long* evals,
+                            int* info);
 
 /* ---- communicator (replaces MPI_COMM_WORLD on the FD / pool paths) ------------------- */
 /* RCCL over xGMI: one process per GPU.  Exchange the 128-byte id out of band (rank 0 creates). */

@@ -20,6 +20,8 @@ PNOL_SEQ_MAX = 64
 LM_SLICES = 8          # PNOL_LM_SLICES: m-slices of the LevMarqMPI J^T J / J^T F summation tree
 SIMPLEX_BATCH_NMAX = 12   # PNOL_SIMPLEX_BATCH_NMAX: the largest n of a batched simplex search
 BFGS_BATCH_NMAX = 12      # PNOL_BFGS_BATCH_NMAX: the largest n of a batched BFGS solve
+BFGS_BND_BATCH_NMAX = 12  # PNOL_BFGS_BND_BATCH_NMAX: the largest n of a batched bounded BFGS solve
+BFGS_BND_BATCH_CORNER = 256   # PNOL_BFGS_BND_BATCH_CORNER: bit 8 of info, a corner end
 
 OBJ_ROSENBROCK, OBJ_POWER, OBJ_QUADRATIC = 0, 1, 4
 OBJ_EXPCURVE, OBJ_CUBIC, OBJ_LINRES = 10, 11, 12
@@ -129,6 +131,9 @@ _SIGS = {
     "pnol_bfgs_batch_solve_d": (_i, [_vp, _vp, _dp, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pnol_run_bfgs_batch": (_i, [_i, _i, _d, _dp, _sz, _dp, _sz, C.c_longlong, _dp, _dp, _dp, _dp, _dp,
                                  C.POINTER(_i), C.POINTER(C.c_longlong)]),
+    "pnol_bfgs_bnd_batch_solve_d": (_i, [_vp, _vp, _dp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pnol_run_bfgs_bnd_batch": (_i, [_i, _i, _d, _dp, _sz, _dp, _sz, C.c_longlong, _dp, _dp, _dp, _dp, _dp, _dp,
+                                     C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(_i)]),
     "pnol_comm_unique_id": (_i, [C.c_char_p]),
     "pnol_comm_init_rccl": (_i, [_vp, _i, _i, C.c_char_p]),
     "pnol_comm_init_host": (_i, [_i, _i, ALLGATHER_FN, _vp]),

@@ -795,4 +795,46 @@ int pnol_run_bfgs_batch(int kind, int n, double power, const double* p0, size_t 
     return st;
 }
 
+// ---- batched box-bounded BFGS (bfgs_bnd_batch.hip) -----------------------------------------
+
+int pnol_bfgs_bnd_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* params, const double* Xlb,
+                                const double* Xub, long long nstart, double* X, double* f0, double* fopt, int* iters,
+                                long long* evals, int* info) {
+    if (!ctx || !obj) return PNOL_ERR_ARG;
+    PNOL_CHECK(bfgs_bnd_batch_check_params(params));
+    PNOL_CHECK(scalar_batch_check_shape(obj->kind, obj->n, nstart, PNOL_BFGS_BND_BATCH_NMAX));
+    if (!Xlb || !Xub || !X || !f0 || !fopt || !iters || !evals || !info || obj->device != ctx->device)
+        return PNOL_ERR_ARG;
+    PNOL_CHECK(set_device(ctx));
+    return launch_bfgs_bnd_batch(ctx, obj, params, Xlb, Xub, nstart, X, f0, fopt, iters, evals, info);
+}
+
+int pnol_run_bfgs_bnd_batch(int kind, int n, double power, const double* p0, size_t len0, const double* p1,
+                            size_t len1, long long nstart, const double* params, const double* Xlb,
+                            const double* Xub, double* X, double* f0, double* fopt, int* iters, long long* evals,
+                            int* info) {
+    PNOL_CHECK(bfgs_bnd_batch_check_params(params));
+    PNOL_CHECK(scalar_batch_check_shape(kind, n, nstart, PNOL_BFGS_BND_BATCH_NMAX));
+    if (kind == PNOL_OBJ_QUADRATIC && (!p0 || !p1 || len0 < (size_t)n || len1 < (size_t)n)) return PNOL_ERR_ARG;
+    if (!Xlb || !Xub || !X || !f0 || !fopt || !iters || !evals || !info) return PNOL_ERR_ARG;
+    for (int i = 0; i < n; ++i)
+        if (!(Xlb[i] <= Xub[i])) return PNOL_ERR_ARG;
+    pnol_ctx* ctx = nullptr;
+    PNOL_CHECK(pnol_default_ctx(&ctx));
+    PNOL_CHECK(set_device(ctx));
+    pnol_dobj* o = nullptr;
+    PNOL_CHECK(pnol_dobj_create(ctx, kind, n, 0, p0, len0, p1, len1, power, &o));
+    const size_t ns = (size_t)nstart;
+    const HostArray arrays[] = {{X, ns * n, 8, kHostIn | kHostOut}, {(void*)Xlb, (size_t)n, 8, kHostIn},
+                                {(void*)Xub, (size_t)n, 8, kHostIn}, {f0, ns, 8, kHostOut},
+                                {fopt, ns, 8, kHostOut},            {evals, ns, 8, kHostOut},
+                                {iters, ns, 4, kHostOut},           {info, ns, 4, kHostOut}};
+    const int st = run_host_block(ctx, arrays, [&](void* const* d) {
+        return launch_bfgs_bnd_batch(ctx, o, params, (const double*)d[1], (const double*)d[2], nstart, (double*)d[0],
+                                     (double*)d[3], (double*)d[4], (int*)d[6], (long long*)d[5], (int*)d[7]);
+    });
+    pnol_dobj_destroy(o);
+    return st;
+}
+
 }  // extern "C"

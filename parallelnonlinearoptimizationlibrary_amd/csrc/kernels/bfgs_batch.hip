@@ -17,9 +17,8 @@
 // n^2 + 6 n doubles per lane: n = 12 -> 216 x 512 B = 108 KB, one workgroup per CU; n = 10 ->
 // 80 KB; n <= 5 -> <= 28 KB.
 //
-// Update in place.  Column j of M1 D needs only column j of D, and row i of (M1 D) M2 only row i
-// of M1 D, so both products go through the n-slot temporary with the per-entry sums of the two
-// GEMMs (l ascending from 0.0, then + M3); the entries of M1, M2, M3 are recomputed where used.
+// Update in place and direction: lane_bfgs_update and lane_bfgs_direction (lane_batch.hpp), shared
+// with bfgs_bnd_batch.hip.
 //
 // Divergence.  Lanes sit in different phases (FD coordinate i, line-search trip, zoom trip).  A
 // lane is a small state machine and the wave one loop with ONE objective call site: each lane
@@ -194,41 +193,11 @@ __global__ __launch_bounds__(kLaneBatchLanes) void k_bfgs_batch(
         if (state == BB_STEP && !gradBusy) {
             if (!first) {
                 // s = alpha p and y = g - gprev (:113-114); updateHessianInv (:389-432)
-                double ys = 0.0;
                 for (int i = 0; i < n; ++i) {
-                    const double si = alpha * p[i * kLaneBatchLanes];
-                    const double yi = g[i * kLaneBatchLanes] - gp[i * kLaneBatchLanes];
-                    p[i * kLaneBatchLanes] = si;
-                    gp[i * kLaneBatchLanes] = yi;
-                    ys = ys + yi * si;
+                    p[i * kLaneBatchLanes] = alpha * p[i * kLaneBatchLanes];
+                    gp[i * kLaneBatchLanes] = g[i * kLaneBatchLanes] - gp[i * kLaneBatchLanes];
                 }
-                const double rho = 1 / ys;
-                for (int j = 0; j < n; ++j) {          // column j of M1 D
-                    for (int i = 0; i < n; ++i) {
-                        const double rs = rho * p[i * kLaneBatchLanes];
-                        double acc = 0.0;
-                        for (int l = 0; l < n; ++l) {
-                            const double e = i == l ? 1.0 : 0.0;
-                            acc = acc + (e - rs * gp[l * kLaneBatchLanes]) * D[(l * n + j) * kLaneBatchLanes];
-                        }
-                        tmp[i * kLaneBatchLanes] = acc;
-                    }
-                    for (int i = 0; i < n; ++i) D[(i * n + j) * kLaneBatchLanes] = tmp[i * kLaneBatchLanes];
-                }
-                for (int i = 0; i < n; ++i) {          // row i of (M1 D) M2, + M3
-                    for (int j = 0; j < n; ++j) {
-                        const double sj = p[j * kLaneBatchLanes];
-                        double acc = 0.0;
-                        for (int l = 0; l < n; ++l) {
-                            const double e = l == j ? 1.0 : 0.0;
-                            acc = acc + D[(i * n + l) * kLaneBatchLanes] * (e - rho * gp[l * kLaneBatchLanes] * sj);
-                        }
-                        tmp[j * kLaneBatchLanes] = acc;
-                    }
-                    const double rs = rho * p[i * kLaneBatchLanes];
-                    for (int j = 0; j < n; ++j)
-                        D[(i * n + j) * kLaneBatchLanes] = tmp[j * kLaneBatchLanes] + rs * p[j * kLaneBatchLanes];
-                }
+                lane_bfgs_update(D, p, gp, tmp, n);
                 double gg = 0.0;
                 for (int i = 0; i < n; ++i) gg = gg + g[i * kLaneBatchLanes] * g[i * kLaneBatchLanes];
                 gnorm = sqrt(gg);
@@ -237,12 +206,8 @@ __global__ __launch_bounds__(kLaneBatchLanes) void k_bfgs_batch(
             first = false;
             if (iter < maxIter && xdiff > xMinDiff && gnorm > minGrad2Norm) {
                 // p = -D g (:52-56), then the line search's start (:177-190)
-                for (int i = 0; i < n; ++i) {
-                    gp[i * kLaneBatchLanes] = g[i * kLaneBatchLanes];
-                    double acc = 0.0;
-                    for (int j = 0; j < n; ++j) acc = acc + D[(i * n + j) * kLaneBatchLanes] * g[j * kLaneBatchLanes];
-                    p[i * kLaneBatchLanes] = -acc;
-                }
+                for (int i = 0; i < n; ++i) gp[i * kLaneBatchLanes] = g[i * kLaneBatchLanes];
+                lane_bfgs_direction(D, g, p, n);
                 double gd = 0.0;
                 for (int i = 0; i < n; ++i) gd = gd + g[i * kLaneBatchLanes] * p[i * kLaneBatchLanes];
                 alpha = 0.0; Fopt = F;

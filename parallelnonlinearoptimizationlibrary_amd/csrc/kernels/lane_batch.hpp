@@ -1,7 +1,8 @@
 // lane_batch.hpp -- what the "one lane per problem, whole algorithm in one launch" kernels share
-// (lm_batch.hip, simplex_batch.hip, bfgs_batch.hip): the lane count, the LDS budget their sizes
-// are bounded by, the launch tail, and for the two scalar-objective solvers the objective's
-// sequential sum over a lane-minor LDS point, the objective check and the kind dispatch.  The
+// (lm_batch.hip, simplex_batch.hip, bfgs_batch.hip, bfgs_bnd_batch.hip): the lane count, the LDS
+// budget their sizes are bounded by, the launch tail, for the scalar-objective solvers the
+// objective's sequential sum over a lane-minor LDS point, the objective check and the kind
+// dispatch, and for the two BFGS solvers the exact inverse-Hessian update and the direction.  The
 // kernels' state machines and LDS layouts are their own.
 #pragma once
 
@@ -28,6 +29,53 @@ __device__ __forceinline__ double lane_eval(const double* xs, int n, const doubl
         xk = xk1;
     }
     return f;
+}
+
+// updateHessianInv (BFGS_with_linesearch.cpp:389-432) of one lane, exact and in place:
+// D <- M1 D M2 + M3 with M1 = I - rho s y^T, M2 = I - rho y s^T, M3 = rho s s^T, rho = 1 / (y . s).
+// D is n x n row-major, s, y and tmp n slots each, all lane-minor (stride kLaneBatchLanes).  Column
+// j of M1 D needs only column j of D, and row i of (M1 D) M2 only row i of M1 D, so both products
+// go through the n-slot temporary with the per-entry sums of the two GEMMs (l ascending from 0.0,
+// then + M3); the entries of M1, M2, M3 are recomputed where used.
+__device__ __forceinline__ void lane_bfgs_update(double* D, const double* s, const double* y, double* tmp, int n) {
+    double ys = 0.0;
+    for (int i = 0; i < n; ++i) ys = ys + y[i * kLaneBatchLanes] * s[i * kLaneBatchLanes];
+    const double rho = 1 / ys;
+    for (int j = 0; j < n; ++j) {          // column j of M1 D
+        for (int i = 0; i < n; ++i) {
+            const double rs = rho * s[i * kLaneBatchLanes];
+            double acc = 0.0;
+            for (int l = 0; l < n; ++l) {
+                const double e = i == l ? 1.0 : 0.0;
+                acc = acc + (e - rs * y[l * kLaneBatchLanes]) * D[(l * n + j) * kLaneBatchLanes];
+            }
+            tmp[i * kLaneBatchLanes] = acc;
+        }
+        for (int i = 0; i < n; ++i) D[(i * n + j) * kLaneBatchLanes] = tmp[i * kLaneBatchLanes];
+    }
+    for (int i = 0; i < n; ++i) {          // row i of (M1 D) M2, + M3
+        for (int j = 0; j < n; ++j) {
+            const double sj = s[j * kLaneBatchLanes];
+            double acc = 0.0;
+            for (int l = 0; l < n; ++l) {
+                const double e = l == j ? 1.0 : 0.0;
+                acc = acc + D[(i * n + l) * kLaneBatchLanes] * (e - rho * y[l * kLaneBatchLanes] * sj);
+            }
+            tmp[j * kLaneBatchLanes] = acc;
+        }
+        const double rs = rho * s[i * kLaneBatchLanes];
+        for (int j = 0; j < n; ++j)
+            D[(i * n + j) * kLaneBatchLanes] = tmp[j * kLaneBatchLanes] + rs * s[j * kLaneBatchLanes];
+    }
+}
+
+// p = -D g of one lane (BFGS_with_linesearch.cpp:52-56): row sums over j ascending from 0.0
+__device__ __forceinline__ void lane_bfgs_direction(const double* D, const double* g, double* p, int n) {
+    for (int i = 0; i < n; ++i) {
+        double acc = 0.0;
+        for (int j = 0; j < n; ++j) acc = acc + D[(i * n + j) * kLaneBatchLanes] * g[j * kLaneBatchLanes];
+        p[i * kLaneBatchLanes] = -acc;
+    }
 }
 
 // The launch tail: `count` items on 64-lane workgroups with `lds` bytes of dynamic LDS (the limit

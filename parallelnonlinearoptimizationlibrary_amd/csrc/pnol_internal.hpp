@@ -382,6 +382,15 @@ inline int bfgs_batch_check_params(const double* p) {
     if (p[10] != 0.0) return PNOL_ERR_UNSUPPORTED;
     return PNOL_OK;
 }
+// the 15 BFGS_Bnd::setParams values of the batched C ABI: maxIterLineSearch (6) and maxIter (10)
+// must be non-negative ints, and the FD initial Hessian (13) is not offered; nothing here touches
+// a device
+inline int bfgs_bnd_batch_check_params(const double* p) {
+    if (!p) return PNOL_ERR_ARG;
+    if (!(p[6] >= 0.0 && p[6] <= 2147483647.0) || !(p[10] >= 0.0 && p[10] <= 2147483647.0)) return PNOL_ERR_ARG;
+    if (p[13] != 0.0) return PNOL_ERR_UNSUPPORTED;
+    return PNOL_OK;
+}
 // Every problem's whole LevMarq::findMin in one launch, one lane per problem (lm_batch.hip).
 // params: host, LevMarq::setParams order; X: x0 in, optimum out; F0 / FOpt nullable
 int launch_lm_batch(pnol_ctx* ctx, const pnol_lm_batch* b, const double* y, const double* params, double* X,
@@ -396,6 +405,13 @@ int launch_simplex_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params
 // optima out
 int launch_bfgs_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, long long nstart, double* X,
                       double* f0, double* fopt, double* gnorm, int* iters, long long* evals);
+// nstart independent BFGS_Bnd::findMinBnd runs of one scalar objective in one box in one launch,
+// one lane per start (bfgs_bnd_batch.hip).  params: host, BFGS_Bnd::setParams order (already
+// checked); Xlb / Xub: device, n each; X: the starts in, the optima out; info: the deepest
+// recursion level | PNOL_BFGS_BND_BATCH_CORNER
+int launch_bfgs_bnd_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, const double* Xlb,
+                          const double* Xub, long long nstart, double* X, double* f0, double* fopt, int* iters,
+                          long long* evals, int* info);
 
 // ---- LM m-slices: J^T J and J^T F are summed over kLmSlices slices of the m
 // residual rows by a fixed tree (syrk.hip), so LevMarqMPI can split the rows over up to

@@ -501,18 +501,24 @@ def _bfgs_batch_params(params):
     return p
 
 
-def _run_scalar_batch(name, nf, to_params, obj, x0, params, extra, kind, power, p0, p1):
+def _run_scalar_batch(name, nf, to_params, obj, x0, params, extra, kind, power, p0, p1, box=None):
     """The shared body of run_simplex_batch / run_bfgs_batch: pnol_<name>_batch_solve_d on obj's
     context, or pnol_run_<name>_batch on host arrays when obj is None.  nf: the per-start double
     outputs (f0, fopt[, gnorm]); to_params: checks params and returns them as an array; extra: the
-    arguments between params and the sizes / X (the simplex's seed).  Returns (X, the nf arrays,
-    iters, evals) as one tuple."""
+    arguments between params and the sizes / X (the simplex's seed); box: (lb, ub) of a bounded
+    solver, n values each, passed like extra (device arrays on obj's context, host arrays otherwise)
+    and answered by one more int32 per start after evals (info).  Returns (X, the nf arrays, iters,
+    evals[, info]) as one tuple."""
     X = np.ascontiguousarray(np.array(x0, dtype=np.float64))
     if X.ndim != 2:
         raise ValueError("x0 must be nstart x n")
     nstart, n = int(X.shape[0]), int(X.shape[1])
     p = to_params(params)
     cap = max(nstart, 1)
+    if box is not None:
+        box = [np.ascontiguousarray(b, dtype=np.float64).ravel() for b in box]
+        if any(b.size != n for b in box):
+            raise ValueError("lb and ub must have n values each")
     if obj is not None:
         if n != obj.n:
             raise ValueError("x0 rows must have the objective's n values")
@@ -523,23 +529,29 @@ def _run_scalar_batch(name, nf, to_params, obj, x0, params, extra, kind, power, 
         fs = [ctx.empty(cap) for _ in range(nf)]
         iters = t.empty(cap, dtype=t.int32, device=dev)
         evals = t.empty(cap, dtype=t.int64, device=dev)
+        boxd = [] if box is None else [ctx.tensor(b) for b in box]
+        tail = [] if box is None else [t.empty(cap, dtype=t.int32, device=dev)]
         entry = f"pnol_{name}_batch_solve_d"
-        L.check(getattr(L.lib(), entry)(ctx.h, obj.h, _dptr(p), *extra, nstart, _ptr(Xd), *[_ptr(f) for f in fs],
-                                        _ptr(iters), _ptr(evals)), entry)
+        L.check(getattr(L.lib(), entry)(ctx.h, obj.h, _dptr(p), *extra, *[_ptr(b) for b in boxd], nstart, _ptr(Xd),
+                                        *[_ptr(f) for f in fs], _ptr(iters), _ptr(evals), *[_ptr(a) for a in tail]),
+                entry)
         ctx.synchronize()
-        return tuple(a.cpu().numpy() for a in (Xd, *fs, iters, evals))
+        return tuple(a.cpu().numpy() for a in (Xd, *fs, iters, evals, *tail))
     a0 = None if p0 is None else np.ascontiguousarray(p0, dtype=np.float64).ravel()
     a1 = None if p1 is None else np.ascontiguousarray(p1, dtype=np.float64).ravel()
     fs = [np.zeros(cap) for _ in range(nf)]
     iters, evals = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int64)
+    tail = [] if box is None else [np.zeros(cap, dtype=np.int32)]
     Xh = X if X.size else np.zeros(1)
     entry = f"pnol_run_{name}_batch"
     L.check(getattr(L.lib(), entry)(kind, n, C.c_double(power), _dptr(a0) if a0 is not None else None,
                                     0 if a0 is None else a0.size, _dptr(a1) if a1 is not None else None,
-                                    0 if a1 is None else a1.size, nstart, _dptr(p), *extra, _dptr(Xh),
+                                    0 if a1 is None else a1.size, nstart, _dptr(p), *extra,
+                                    *[_dptr(b) for b in box or ()], _dptr(Xh),
                                     *[_dptr(f) for f in fs], iters.ctypes.data_as(C.POINTER(C.c_int)),
-                                    evals.ctypes.data_as(C.POINTER(C.c_longlong))), entry)
-    return (X, *[f[:nstart] for f in fs], iters[:nstart], evals[:nstart])
+                                    evals.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                    *[a.ctypes.data_as(C.POINTER(C.c_int)) for a in tail]), entry)
+    return (X, *[f[:nstart] for f in fs], iters[:nstart], evals[:nstart], *[a[:nstart] for a in tail])
 
 
 def run_simplex_batch(obj, x0, params, seed, kind=None, power=2.0, p0=None, p1=None):
@@ -560,6 +572,26 @@ def run_bfgs_batch(obj, x0, params, kind=None, power=2.0, p0=None, p1=None):
     objective then given by kind / power / p0 / p1.  Returns (X, f0, fopt, gnorm, iters, evals) as
     numpy arrays; gnorm is the loop's last gradient norm."""
     return _run_scalar_batch("bfgs", 3, _bfgs_batch_params, obj, x0, params, (), kind, power, p0, p1)
+
+
+def _bfgs_bnd_batch_params(params):
+    p = np.array(params, dtype=np.float64)
+    if p.size != 15:
+        raise ValueError("params: the 15 values of BFGS_Bnd::setParams")
+    return p
+
+
+def run_bfgs_bnd_batch(obj, x0, lb, ub, params, kind=None, power=2.0, p0=None, p1=None):
+    """Batched box-bounded BFGS: the nstart rows of x0 (nstart x n) are independent
+    BFGS_Bnd::findMinBnd runs of one scalar objective in the box [lb, ub] (n values each, shared by
+    all starts) in one launch; params = BFGS_Bnd::setParams (15 values; initHessFD must be 0).
+    obj: a DeviceObjective (solved on its context through pnol_bfgs_bnd_batch_solve_d), or None
+    for the process default context through the host-pointer entry point pnol_run_bfgs_bnd_batch,
+    the objective then given by kind / power / p0 / p1.  Returns (X, f0, fopt, iters, evals, info)
+    as numpy arrays; iters is totalIter, info the deepest recursion level in bits 0-7 and
+    BFGS_BND_BATCH_CORNER for a start that ended at a corner end (pnol_amd.h)."""
+    return _run_scalar_batch("bfgs_bnd", 2, _bfgs_bnd_batch_params, obj, x0, params, (), kind, power, p0, p1,
+                             box=(lb, ub))
 
 
 def run_levmarq(obj: DeviceObjective, x0, params, which=0, host_eval=False):
