@@ -55,7 +55,8 @@ int pnol_default_ctx(pnol_ctx** out);
 /* Per-kernel HIP-event timers on the context's stream (off by default).  Names: "fd_jacobian",
  * "fd_ckpt", "fd_gradient", "linres_eval", "syrk", "syrk_reduce", "jtr", "solve", "hg",
  * "bfgs_pass", "allgather", "exchange_J", "exchange_A", "lm_batch", "simplex_batch",
- * "bfgs_batch", "bfgs_bnd_batch".  total_ms sums the recorded launches since the last reset.  on = 2 times only
+ * "bfgs_batch", "bfgs_bnd_batch", "ga_batch".  total_ms sums the recorded launches since the last reset.  on = 2
+ * times only
  * "fd_jacobian", "fd_ckpt", "syrk", "exchange_J", "allgather", "hg" and "bfgs_pass" (fewer event
  * records between launches). */
 int pnol_ctx_enable_timers(pnol_ctx* ctx, int on);
@@ -479,6 +480,52 @@ int pnol_run_bfgs_bnd_batch(int kind, int n, double power, const double* p0, siz
                             size_t len1, long long nstart, const double* params, const double* Xlb,
                             const double* Xub, double* X, double* f0, double* fopt, int* iters, long long* evals,
                             int* info);
+
+/* ---- batched genetic algorithm: many independent GeneticAlgorithm runs in one launch ------ */
+/* The limits of a batched run: its two populations, F, Fnew, the fitness and the evaluation
+ * flags, (2 n + 3) doubles and one int per member (members padded to 64), live in the LDS of
+ * one 64-lane workgroup (55 KB at n = 12, Npop = 256). */
+#define PNOL_GA_BATCH_NMAX 12
+#define PNOL_GA_BATCH_NPOP_MAX 256
+/* the most candidate pairs one selection may consume before the run is ended as stuck */
+#define PNOL_GA_BATCH_SELECT_CAP 1048576
+/* bit 0 of info: the run ended on a selection that cannot accept (below) */
+#define PNOL_GA_BATCH_STUCK 1
+/* nrun independent GeneticAlgorithm::findMinBnd runs (GeneticAlgorithm.cpp:12-297) of one scalar
+ * device objective -- PNOL_OBJ_ROSENBROCK, PNOL_OBJ_POWER or PNOL_OBJ_QUADRATIC; other kinds
+ * PNOL_ERR_UNSUPPORTED -- in one box shared by all runs, queued on the context stream with no
+ * host wait (timer "ga_batch"): one 64-lane workgroup runs one whole run, the population's
+ * members on its lanes, through every statement of the host class in order.  Run s draws from the
+ * stream seeded seed + s, so it is GeneticAlgorithm with setSeed(seed + s) from X[s] -- the same
+ * bits of X, f0, fOpt, generations and evaluations, whatever batch it is in (Power with
+ * power != 2 calls the device pow and is not bitwise against the host).  params: HOST, 10 doubles
+ * in setGAParams order without graph (Npop, maxGenerations, eliteFrac, crossFrac,
+ * eliteMutationFrac, mutationSize, eliteMutationSize, initialPopScaling, NstaticGenerations,
+ * verbose), the array pnol_run_ga takes; verbose is accepted and nothing is printed.
+ * PNOL_ERR_ARG, before any device use, when nrun <= 0, Npop < 2, a fraction's member count
+ * ceil(frac * Npop) is negative or not a number, Nrand = Npop - Nelite - NeliteMut - Ncross <= 0
+ * (the reference's "666" exit), or maxGenerations is negative, NaN or does not fit an int;
+ * PNOL_ERR_UNSUPPORTED when n > PNOL_GA_BATCH_NMAX or Npop > PNOL_GA_BATCH_NPOP_MAX.  Xlb / Xub: n
+ * device doubles each.  X: nrun * n device doubles, the starts in and the best members out; f0 /
+ * fopt: nrun doubles; gens: nrun ints (getGenerations()); evals: nrun long longs, the objective
+ * evaluations; info: nrun ints.  The one departure from the host class: a host selection never
+ * returns when no member past index 0 can be accepted (fitness[k] / maxFitness is NaN or 0 for
+ * every k >= 1 although some fitness is positive, e.g. after F overflowed to inf).  A run whose
+ * generation starts in that state, or one of whose selections has rejected
+ * PNOL_GA_BATCH_SELECT_CAP candidate pairs, ends there: X is the current best member, fopt its F,
+ * gens and evals as counted up to there, bit 0 of info (PNOL_GA_BATCH_STUCK) set; everything
+ * before is the host's arithmetic.  The environment variable PNOL_GA_SPEC (1..64, default 64) sets
+ * how many candidate pairs of a selection are tested at once: a tuning knob, every width gives
+ * the same bits.  The reference has no batched form: this replaces a host loop of seeded runs. */
+int pnol_ga_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* params, unsigned long long seed,
+                          const double* Xlb, const double* Xub, long long nrun, double* X, double* f0, double* fopt,
+                          int* gens, long long* evals, int* info);
+/* The same with HOST pointers on the process default context: create the objective (kind, n,
+ * power, p0 / p1 as pnol_dobj_create), upload, solve, download, destroy.  Arguments are checked
+ * before any device use; PNOL_ERR_NODEVICE without a gfx950 device. */
+int pnol_run_ga_batch(int kind, int n, double power, const double* p0, size_t len0, const double* p1, size_t len1,
+                      long long nrun, const double* params, unsigned long long seed, const double* Xlb,
+                      const double* Xub, double* X, double* f0, double* fopt, int* gens, long long* evals, int* info);
 
 /* ---- communicator (replaces MPI_COMM_WORLD on the FD / pool paths) ------------------- */
 /* RCCL over xGMI: one process per GPU.  Exchange the 128-byte id out of band (rank 0 creates). */

@@ -5,7 +5,7 @@ drop-in classes of include/*.hpp).  This package only loads and drives it:
   _lib      ctypes binding of every C-ABI entry point
   device    torch-tensor wrappers (Context, DeviceObjective, LMBatch, run_bfgs, run_levmarq,
             run_levmarq_batch, run_simplex, host_run_simplex, run_simplex_batch, run_bfgs_batch,
-            run_bfgs_bnd_batch)
+            run_bfgs_bnd_batch, run_ga_batch)
   dist      RCCL communicator bootstrap over torch.distributed (one process per GPU)
   build     hipcc build of the library (used by __graft_entry__.build())
 """

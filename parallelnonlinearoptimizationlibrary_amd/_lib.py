@@ -22,6 +22,9 @@ SIMPLEX_BATCH_NMAX = 12   # PNOL_SIMPLEX_BATCH_NMAX: the largest n of a batched 
 BFGS_BATCH_NMAX = 12      # PNOL_BFGS_BATCH_NMAX: the largest n of a batched BFGS solve
 BFGS_BND_BATCH_NMAX = 12  # PNOL_BFGS_BND_BATCH_NMAX: the largest n of a batched bounded BFGS solve
 BFGS_BND_BATCH_CORNER = 256   # PNOL_BFGS_BND_BATCH_CORNER: bit 8 of info, a corner end
+GA_BATCH_NMAX = 12        # PNOL_GA_BATCH_NMAX: the largest n of a batched GA run
+GA_BATCH_NPOP_MAX = 256   # PNOL_GA_BATCH_NPOP_MAX: the largest population of a batched GA run
+GA_BATCH_STUCK = 1        # PNOL_GA_BATCH_STUCK: bit 0 of info, ended on a selection that cannot accept
 
 OBJ_ROSENBROCK, OBJ_POWER, OBJ_QUADRATIC = 0, 1, 4
 OBJ_EXPCURVE, OBJ_CUBIC, OBJ_LINRES = 10, 11, 12
@@ -134,6 +137,10 @@ _SIGS = {
     "pnol_bfgs_bnd_batch_solve_d": (_i, [_vp, _vp, _dp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pnol_run_bfgs_bnd_batch": (_i, [_i, _i, _d, _dp, _sz, _dp, _sz, C.c_longlong, _dp, _dp, _dp, _dp, _dp, _dp,
                                      C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(_i)]),
+    "pnol_ga_batch_solve_d": (_i, [_vp, _vp, _dp, C.c_ulonglong, _vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _vp,
+                                   _vp]),
+    "pnol_run_ga_batch": (_i, [_i, _i, _d, _dp, _sz, _dp, _sz, C.c_longlong, _dp, C.c_ulonglong, _dp, _dp, _dp, _dp,
+                               _dp, C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(_i)]),
     "pnol_comm_unique_id": (_i, [C.c_char_p]),
     "pnol_comm_init_rccl": (_i, [_vp, _i, _i, C.c_char_p]),
     "pnol_comm_init_host": (_i, [_i, _i, ALLGATHER_FN, _vp]),

@@ -837,4 +837,53 @@ int pnol_run_bfgs_bnd_batch(int kind, int n, double power, const double* p0, siz
     return st;
 }
 
+// ---- batched genetic algorithm (ga_batch.hip) ---------------------------------------------
+namespace {
+
+// params, kind and sizes of a GA batch, shared by the device- and the host-pointer call; nothing
+// here touches a device
+int ga_batch_check(const double* params, int kind, int n, long long nrun) {
+    GaCounts c;
+    PNOL_CHECK(ga_batch_check_params(params, &c));
+    PNOL_CHECK(scalar_batch_check_shape(kind, n, nrun, PNOL_GA_BATCH_NMAX));
+    return c.Npop > PNOL_GA_BATCH_NPOP_MAX ? PNOL_ERR_UNSUPPORTED : PNOL_OK;
+}
+
+}  // namespace
+
+int pnol_ga_batch_solve_d(pnol_ctx* ctx, pnol_dobj* obj, const double* params, unsigned long long seed,
+                          const double* Xlb, const double* Xub, long long nrun, double* X, double* f0, double* fopt,
+                          int* gens, long long* evals, int* info) {
+    if (!ctx || !obj) return PNOL_ERR_ARG;
+    PNOL_CHECK(ga_batch_check(params, obj->kind, obj->n, nrun));
+    if (!Xlb || !Xub || !X || !f0 || !fopt || !gens || !evals || !info || obj->device != ctx->device)
+        return PNOL_ERR_ARG;
+    PNOL_CHECK(set_device(ctx));
+    return launch_ga_batch(ctx, obj, params, seed, Xlb, Xub, nrun, X, f0, fopt, gens, evals, info);
+}
+
+int pnol_run_ga_batch(int kind, int n, double power, const double* p0, size_t len0, const double* p1, size_t len1,
+                      long long nrun, const double* params, unsigned long long seed, const double* Xlb,
+                      const double* Xub, double* X, double* f0, double* fopt, int* gens, long long* evals, int* info) {
+    PNOL_CHECK(ga_batch_check(params, kind, n, nrun));
+    if (kind == PNOL_OBJ_QUADRATIC && (!p0 || !p1 || len0 < (size_t)n || len1 < (size_t)n)) return PNOL_ERR_ARG;
+    if (!Xlb || !Xub || !X || !f0 || !fopt || !gens || !evals || !info) return PNOL_ERR_ARG;
+    pnol_ctx* ctx = nullptr;
+    PNOL_CHECK(pnol_default_ctx(&ctx));
+    PNOL_CHECK(set_device(ctx));
+    pnol_dobj* o = nullptr;
+    PNOL_CHECK(pnol_dobj_create(ctx, kind, n, 0, p0, len0, p1, len1, power, &o));
+    const size_t ns = (size_t)nrun;
+    const HostArray arrays[] = {{X, ns * n, 8, kHostIn | kHostOut}, {(void*)Xlb, (size_t)n, 8, kHostIn},
+                                {(void*)Xub, (size_t)n, 8, kHostIn}, {f0, ns, 8, kHostOut},
+                                {fopt, ns, 8, kHostOut},            {evals, ns, 8, kHostOut},
+                                {gens, ns, 4, kHostOut},            {info, ns, 4, kHostOut}};
+    const int st = run_host_block(ctx, arrays, [&](void* const* d) {
+        return launch_ga_batch(ctx, o, params, seed, (const double*)d[1], (const double*)d[2], nrun, (double*)d[0],
+                               (double*)d[3], (double*)d[4], (int*)d[6], (long long*)d[5], (int*)d[7]);
+    });
+    pnol_dobj_destroy(o);
+    return st;
+}
+
 }  // extern "C"

@@ -4,6 +4,8 @@
 // objective's sequential sum over a lane-minor LDS point, the objective check and the kind
 // dispatch, and for the two BFGS solvers the exact inverse-Hessian update and the direction.  The
 // kernels' state machines and LDS layouts are their own.
+// ga_batch.hip (one wave per run, not one lane per problem) uses lane_eval, the objective check, the
+// kind dispatch and the workgroup-count form of the launch tail.
 #pragma once
 
 #include <type_traits>
@@ -78,11 +80,10 @@ __device__ __forceinline__ void lane_bfgs_direction(const double* D, const doubl
     }
 }
 
-// The launch tail: `count` items on 64-lane workgroups with `lds` bytes of dynamic LDS (the limit
-// is raised only above the 64 KB every kernel has) on the context stream, timed under `timer`
+// The launch tail: `blocks` 64-lane workgroups with `lds` bytes of dynamic LDS (the limit is
+// raised only above the 64 KB every kernel has) on the context stream, timed under `timer`
 template <typename Kernel, typename... Args>
-int lane_batch_launch(pnol_ctx* ctx, const char* timer, Kernel kern, size_t count, size_t lds, Args... args) {
-    const size_t blocks = (count + kLaneBatchLanes - 1) / kLaneBatchLanes;
+int wave_batch_launch(pnol_ctx* ctx, const char* timer, Kernel kern, size_t blocks, size_t lds, Args... args) {
     if (blocks > 0x7fffffffull) return PNOL_ERR_ARG;
     if (lds > 64 * 1024)
         PNOL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -90,6 +91,11 @@ int lane_batch_launch(pnol_ctx* ctx, const char* timer, Kernel kern, size_t coun
     ScopedTimer tm(ctx, timer);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kLaneBatchLanes), lds, ctx->stream, args...);
     return launch_check();
+}
+// the one-lane-per-problem form: `count` problems, 64 to a workgroup
+template <typename Kernel, typename... Args>
+int lane_batch_launch(pnol_ctx* ctx, const char* timer, Kernel kern, size_t count, size_t lds, Args... args) {
+    return wave_batch_launch(ctx, timer, kern, (count + kLaneBatchLanes - 1) / kLaneBatchLanes, lds, args...);
 }
 
 // the objective of a scalar-objective batch: there, 1 <= n <= nmax, a quadratic's data n long

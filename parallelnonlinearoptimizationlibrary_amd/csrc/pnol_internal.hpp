@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <functional>
@@ -412,6 +413,38 @@ int launch_bfgs_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, l
 int launch_bfgs_bnd_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, const double* Xlb,
                           const double* Xub, long long nstart, double* X, double* f0, double* fopt, int* iters,
                           long long* evals, int* info);
+
+// The member counts of a GA generation from the 10 setGAParams values of the batched C ABI
+// (GeneticAlgorithm.cpp:24-44, the host class's expressions); nothing here touches a device
+struct GaCounts {
+    int Npop, maxGen, Nelite, NeliteMut, Ncross, Nrand;
+};
+// PNOL_ERR_ARG: Npop < 2 (or not an int), maxGenerations negative, NaN or past an int, a member
+// count negative or NaN, Nrand <= 0
+inline int ga_batch_check_params(const double* p, GaCounts* out) {
+    if (!p) return PNOL_ERR_ARG;
+    if (!(p[0] >= 2.0 && p[0] <= 2147483647.0) || !(p[1] >= 0.0 && p[1] <= 2147483647.0)) return PNOL_ERR_ARG;
+    GaCounts c;
+    c.Npop = (int)p[0];
+    c.maxGen = (int)p[1];
+    const double ce = std::ceil(p[2] * c.Npop), cx = std::ceil(p[3] * c.Npop), cm = std::ceil(p[4] * c.Npop);
+    if (!(ce >= 0.0 && ce <= c.Npop) || !(cx >= 0.0 && cx <= c.Npop) || !(cm >= 0.0 && cm <= c.Npop))
+        return PNOL_ERR_ARG;
+    c.Nelite = (int)ce;
+    c.Ncross = (int)cx;
+    c.NeliteMut = (int)cm;
+    c.Nrand = c.Npop - c.Nelite - c.NeliteMut - c.Ncross;
+    if (c.Nrand <= 0) return PNOL_ERR_ARG;
+    if (out) *out = c;
+    return PNOL_OK;
+}
+// nrun independent GeneticAlgorithm::findMinBnd runs of one scalar objective in one box in one
+// launch, one 64-lane workgroup per run (ga_batch.hip).  params: host, setGAParams order without
+// graph (already checked); run s draws from the stream seeded seed + s; Xlb / Xub: device, n
+// each; X: the starts in, the best members out; info: PNOL_GA_BATCH_STUCK
+int launch_ga_batch(pnol_ctx* ctx, const pnol_dobj* o, const double* params, unsigned long long seed,
+                    const double* Xlb, const double* Xub, long long nrun, double* X, double* f0, double* fopt,
+                    int* gens, long long* evals, int* info);
 
 // ---- LM m-slices: J^T J and J^T F are summed over kLmSlices slices of the m
 // residual rows by a fixed tree (syrk.hip), so LevMarqMPI can split the rows over up to

@@ -502,7 +502,7 @@ def _bfgs_batch_params(params):
 
 
 def _run_scalar_batch(name, nf, to_params, obj, x0, params, extra, kind, power, p0, p1, box=None):
-    """The shared body of run_simplex_batch / run_bfgs_batch: pnol_<name>_batch_solve_d on obj's
+    """The shared body of run_simplex_batch, run_bfgs_batch, run_bfgs_bnd_batch and run_ga_batch: pnol_<name>_batch_solve_d on obj's
     context, or pnol_run_<name>_batch on host arrays when obj is None.  nf: the per-start double
     outputs (f0, fopt[, gnorm]); to_params: checks params and returns them as an array; extra: the
     arguments between params and the sizes / X (the simplex's seed); box: (lb, ub) of a bounded
@@ -591,6 +591,29 @@ def run_bfgs_bnd_batch(obj, x0, lb, ub, params, kind=None, power=2.0, p0=None, p
     as numpy arrays; iters is totalIter, info the deepest recursion level in bits 0-7 and
     BFGS_BND_BATCH_CORNER for a start that ended at a corner end (pnol_amd.h)."""
     return _run_scalar_batch("bfgs_bnd", 2, _bfgs_bnd_batch_params, obj, x0, params, (), kind, power, p0, p1,
+                             box=(lb, ub))
+
+
+GA_DEFAULTS = (100, 1000, 0.1, 0.3, 0.2, 0.5, 0.01, 0.5, 50, 0)   # GeneticAlgorithm's constructor
+
+
+def _ga_batch_params(params):
+    p = np.array(params, dtype=np.float64)
+    if p.size != 10:
+        raise ValueError("params: the 10 values of GeneticAlgorithm::setGAParams without graph")
+    return p
+
+
+def run_ga_batch(obj, x0, lb, ub, params, seed, kind=None, power=2.0, p0=None, p1=None):
+    """Batched genetic algorithm: the nrun rows of x0 (nrun x n) are independent
+    GeneticAlgorithm::findMinBnd runs of one scalar objective in the box [lb, ub] (n values each,
+    shared by all runs) in one launch, run s on the stream seeded seed + s; params = setGAParams
+    without graph (10 values, as run_ga takes).  obj: a DeviceObjective (solved on its context
+    through pnol_ga_batch_solve_d), or None for the process default context through the
+    host-pointer entry point pnol_run_ga_batch, the objective then given by kind / power / p0 / p1.
+    Returns (X, f0, fopt, generations, evals, info) as numpy arrays; info is GA_BATCH_STUCK for a
+    run that ended on a selection that cannot accept (pnol_amd.h)."""
+    return _run_scalar_batch("ga", 2, _ga_batch_params, obj, x0, params, (seed,), kind, power, p0, p1,
                              box=(lb, ub))
 
 
